@@ -14,7 +14,12 @@ One "step" = one evaluation of the stage-3 fitting closure (objective forward + 
 decode, 3 SMPL evaluations (64-vertex subset kernels), HuMoR roll-out (59 steps, prior + decoder) with its adjoint, all loss terms -- the
 deterministic unit of "fitting-iter/sec" (an L-BFGS outer iteration is ~25 of these).  Inputs are resident in HBM.
 `value` = closure evaluations per second x (global batch / 32), i.e. aggregate 32x60-batch closure evaluations per second.
-Also reported: `smpl_verts_per_sec` (dense 6890-vertex SMPL forward, N=1920), the `roofline` of the streaming LBS kernel
+A plain run does only what `value` needs: set-up (at N=1 the one-off graph-vs-eager probe that picks the timed closure mode),
+W warm-up and K timed closure evaluations, the result line.  `--dump-outputs DIR` writes what the last timed evaluation returned
+to its caller -- `loss.npy` (float64) and `grad_<variable>.npy` (float32) for every optimisation variable -- for output-for-output
+comparison of two builds (the inputs are seeded: identical from run to run).
+With `--full` the side measurements below are taken as well (the `--no-*` options switch single ones off):
+`smpl_verts_per_sec` (dense 6890-vertex SMPL forward, N=1920), the `roofline` of the streaming LBS kernel
 (HIP events on the launch stream), `lbfgs` (REAL torch.optim.LBFGS outer iterations of every stage / stage-3 phase through
 MotionOptimizer.run: outer iterations/s, closure evaluations per outer iteration, and the whole-fit time they imply for the
 reference's 30/80/70 schedule), `strong` (N>1: the same 32-sequence job sharded over the N GPUs, next to the weak-scaling
@@ -81,6 +86,10 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true', help='also take every side measurement (rooflines, scaling companions, L-BFGS profile, '
+                    'RCCL figures, C5 sizes, CPU baseline + parity); a plain run times the headline closure only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss and the gradients of the last timed closure evaluation as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--eager', action='store_true', help='do not capture the closure into a hipGraph')
     ap.add_argument('--no-c5', action='store_true', help='skip the BASELINE C5-size (256x120) kernel rooflines appended at N=1')
@@ -183,9 +192,19 @@ class FitClosure:
             self.params, None)
 
     def step(self):
-        return self.closure()
+        self.last_loss = self.closure()
+        return self.last_loss
 
     VAR_NAMES = ('latent_motion', 'betas', 'floor_plane', 'trans', 'root_orient', 'latent_pose', 'trans_vel', 'joints_vel', 'root_orient_vel')
+
+    def outputs(self):
+        """What the LAST evaluation returned to its caller (no new evaluation): the loss and every variable's gradient, on the host."""
+        o = self.opt
+        out = {'loss': np.asarray(float(self.last_loss.detach()), dtype=np.float64)}
+        for k in self.VAR_NAMES:
+            g = getattr(o, k).grad
+            out['grad_' + k] = (g.detach().float().cpu().numpy() if g is not None else np.zeros(tuple(getattr(o, k).shape), np.float32))
+        return out
 
     def snapshot(self):
         """One evaluation: the variables it was evaluated at, its loss and every gradient, on the host (parity vs the oracle)."""
@@ -576,6 +595,12 @@ def cpu_baseline(npz, gpu_eval=None):
                       f'59-step Python roll-out loop, VPoser, all loss terms), torch CPU'}
 
 
+def dump_outputs(outdir, arrays):
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher (WORLD_SIZE unset): start the N ranks ourselves, one per GPU, exactly as the
     driver's torch.distributed.run command line would, and relay rank 0's JSON line."""
@@ -696,8 +721,11 @@ def run(args):
             d = t.item()
         return d
     dt = timed(fc)
+    if args.dump_outputs and rank == 0:
+        # read before anything else evaluates a closure (a sharded closure's gradients live in an arena the next evaluation zero-fills)
+        dump_outputs(args.dump_outputs, fc.outputs())
     roof_early = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # the roofline kernel at the metric's batch, measured right behind the headline timing: behind the 256 x 120 closure / the C5 sizes the
         # chip sits in a power-management transient (MI355X_MICROARCH.md, DVFS give-back; profiles/r02_run20_skin_jitter.txt) that cost this
         # HBM-bound kernel 5-10 % in the round-5 runs (0.59-0.62 measured there against 0.63-0.65 of the rounds that measured it first)
@@ -710,7 +738,7 @@ def run(args):
     #              at N = 8).  Chain-bound: a rank's closure is a 59-step dependent chain whatever its share is.
     #   c5_weak -- BASELINE config 5's shape per GPU: 32 sub-sequences x 120 frames on every rank (256 x 120 at N = 8).
     strong = None
-    if world > 1 and args.scaling in ('strong', 'both') and B_SEQ >= world:
+    if args.full and world > 1 and args.scaling in ('strong', 'both') and B_SEQ >= world:
         del fc
         torch.cuda.empty_cache()
         fc = FitClosure(dev, npz, world, rank, None, use_graphs=False, B_total=B_SEQ)
@@ -722,7 +750,7 @@ def run(args):
         strong = {'scaling': 'strong', 'global_batch': B_SEQ, 'sequences_per_gpu': [B_SEQ], 'value': round(args.steps / dt, 3),
                   'unit': 'closure-evals/s of the one 32x60 job', 'ms_per_step': round(dt / args.steps * 1e3, 4), 'note': 'N = 1: the same run as `value`'}
     c5_weak = None
-    if not args.no_c5_weak:
+    if args.full and not args.no_c5_weak:
         keep = fc
         f5 = FitClosure(dev, npz, world, rank, None, use_graphs=False, T=120)
         f5.mode_note = None
@@ -733,7 +761,7 @@ def run(args):
         c5_weak = {'scaling': 'weak', 'workload': f'32 sub-sequences x 120 frames per GPU ({B_SEQ * world} x 120 in all; BASELINE config 5 is 256 x 120 = N 8)',
                    'value': round(args.steps * world / dt5, 3), 'unit': 'closure-evals/s (32x120-batch equivalents)', 'ms_per_step': round(dt5 / args.steps * 1e3, 4)}
     c5_full = None
-    if world == 1 and not args.no_c5_weak:
+    if args.full and world == 1 and not args.no_c5_weak:
         # BASELINE config 5 as it stands (256 sub-sequences x 120 frames) as ONE stage-3 closure on one GPU: the roll-out runs on the
         # pipelined persistent kernels (rollout_pipe.inc), SMPL / losses on 30 720 frames
         try:
@@ -759,7 +787,7 @@ def run(args):
             c5_full = {'error': '%s: %s' % (type(e).__name__, str(e)[:300])}
             torch.cuda.empty_cache()
     coll = None
-    if dist is not None:
+    if args.full and dist is not None:
         n = sum(p.numel() for p in fc.params) + 1
         packed = torch.zeros(n, device=dev)
         halo = torch.zeros(T_SEQ * 43 * 3 + 16 + 3, device=dev)
@@ -771,13 +799,6 @@ def run(args):
                 'collectives_per_closure': '1 differentiable halo all-gather (+ its all-reduce in backward) + 1 packed [gradient | loss] all-reduce'}
 
     if rank == 0:
-        gpu_eval = fc.snapshot() if world == 1 and not args.no_cpu_baseline else None      # for the parity field (untimed)
-        if gpu_eval is not None:
-            gpu_eval['gpu_unstable'] = fc.gradient_sensitivity()
-        # the roofline kernel at the metric's batch, HBM figure: launches rotate over 4 operand sets (1.27 GB: > 256 MiB of other
-        # lines between two uses of any line); the single-set (Infinity-Cache-assisted) figure of rounds 1-2 is kept beside it
-        roof = roof_early
-        ms_dense, ms_dense_fb = dense_smpl_ms(dev, npz)
         res = {
             'metric': 'fitting closure evaluations/s (stage-3 objective fwd+bwd), batch=32 seq=60 per GPU',
             'value': round(args.steps * world / dt, 3), 'unit': 'closure-evals/s (32x60-batch equivalents)',
@@ -798,15 +819,24 @@ def run(args):
                        'global_batch': B_SEQ * world, 'strong_global_batch': B_SEQ, 'seq_len': T_SEQ,
                        'parallelism': f'dp{world} (sub-sequence sharding, replicated L-BFGS)'},
             'closure_mode': closure_mode(args, fc),
+        }
+        if strong is not None:
+            res['strong'] = strong
+    if rank == 0 and args.full:
+        gpu_eval = fc.snapshot() if world == 1 and not args.no_cpu_baseline else None      # for the parity field (untimed)
+        if gpu_eval is not None:
+            gpu_eval['gpu_unstable'] = fc.gradient_sensitivity()
+        ms_dense, ms_dense_fb = dense_smpl_ms(dev, npz)
+        res.update({
             'smpl_verts_per_sec': round(B_SEQ * T_SEQ * V / (ms_dense * 1e-3), 1),
             'smpl_dense_fwd_ms': round(ms_dense, 4),
             'smpl_dense_fwd_bwd_ms': round(ms_dense_fb, 4),
             'smpl_verts_per_sec_fwd_bwd': round(B_SEQ * T_SEQ * V / (ms_dense_fb * 1e-3), 1),
             'rollout': rollout_c4_ms(dev),
-            'roofline': roof,
-        }
-        if strong is not None:
-            res['strong'] = strong
+            # the roofline kernel at the metric's batch, HBM figure: launches rotate over 4 operand sets (1.27 GB: > 256 MiB of other
+            # lines between two uses of any line); the single-set (Infinity-Cache-assisted) figure of rounds 1-2 is kept beside it
+            'roofline': roof_early,
+        })
         if c5_weak is not None:
             res['c5_weak'] = c5_weak
         if c5_full is not None:
@@ -841,6 +871,7 @@ def run(args):
         if not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed on rank 0 of the 1-GPU run only
             res['cpu_baseline'] = cpu_baseline(npz, gpu_eval)
             res['parity'] = res['cpu_baseline'].pop('parity')
+    if rank == 0:
         # the contract's keys first (a reader that truncates the line keeps them), the detailed side measurements after
         head = ['metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'north_star_job', 'strong_value',
                 'strong_ms_per_step', 'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline', 'parity', 'outer_iters_per_sec', 'smpl_verts_per_sec', 'closure_mode',

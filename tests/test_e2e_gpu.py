@@ -209,14 +209,15 @@ def test_stitched_rgb_result_round_trip(gpu_lib, dev, smplh_npz, tmp_path):
 def test_bench_starts_n_ranks_itself(gpu_lib):
     """`python bench.py --gpus 2` with no launcher in front of it must start two ranks (it used to run one and print
     n_gpus 1).  On the one-GPU test box both ranks share cuda:0 and the collectives go through gloo (host staging): the numbers mean
-    nothing, the line's shape does -- n_gpus = 2, a global batch of 64 sub-sequences, the strong-scaling companion, the collectives."""
+    nothing, the line's shape does -- n_gpus = 2, a global batch of 64 sub-sequences, the strong-scaling companion, the collectives
+    (the last two are side measurements: --full)."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
     env = dict(os.environ, HUMOR_AMD_BENCH_BACKEND='gloo', HUMOR_AMD_BENCH_ONE_GPU='1', HUMOR_AMD_ROLLOUT_PERSIST='0')
     env.pop('WORLD_SIZE', None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]

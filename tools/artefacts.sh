@@ -12,10 +12,10 @@ if [ "$2" != "skip-tests" ]; then
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1; tail -1 $OUT/smoke.txt
   echo "smoke: $(( $(date +%s) - t0 )) s"; t0=$(date +%s)
 fi
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; head -c 2500 $OUT/bench.json; echo; tail -2 $OUT/bench.err | cut -c1-300
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; head -c 2500 $OUT/bench.json; echo; tail -2 $OUT/bench.err | cut -c1-300
 echo "bench: $(( $(date +%s) - t0 )) s"; t0=$(date +%s)
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python $R/bench.py --no-cpu-baseline --no-lbfgs --no-rccl-check > $OUT/prof_bench_stdout.txt 2> $OUT/prof_bench_stderr.txt
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python $R/bench.py --full --no-cpu-baseline --no-lbfgs --no-rccl-check > $OUT/prof_bench_stdout.txt 2> $OUT/prof_bench_stderr.txt
 echo "rocprof: $(( $(date +%s) - t0 )) s"
 find $OUT -name "*.db" -delete
 find $OUT/prof -name "*kernel_trace.csv" -delete

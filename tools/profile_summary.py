@@ -14,7 +14,7 @@ def main():
     rows = list(csv.DictReader(open(os.path.join(d, 'bench_kernel_stats.csv'))))
     tot = sum(float(r['TotalDurationNs']) for r in rows)
     ours = sum(float(r['TotalDurationNs']) for r in rows if 'ha::' in r['Name'])
-    out = [f'{os.path.basename(d)} -- rocprofv3 --kernel-trace --stats of `python bench.py --no-cpu-baseline --no-lbfgs --no-rccl-check` on one MI355X', note,
+    out = [f'{os.path.basename(d)} -- rocprofv3 --kernel-trace --stats of `python bench.py --full --no-cpu-baseline --no-lbfgs --no-rccl-check` on one MI355X', note,
            f"bench (un-profiled run, same box): {b['ms_per_step']:.3f} ms/closure = {b['value']:.1f} closure-evals/s; {b.get('closure_mode', '')}",
            f'total kernel time {tot / 1e6:.1f} ms over {sum(int(r["Calls"]) for r in rows)} dispatches; humor_amd kernels {100 * ours / tot:.1f} % of it', '',
            f'{"kernel":<80} {"calls":>7} {"total ms":>9} {"avg us":>9} {"min us":>8} {"%":>6}']
