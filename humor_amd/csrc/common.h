@@ -32,15 +32,6 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// returnless hardware fp32 add at the L2 / memory side (global_atomic_add_f32; no compare-and-swap loop)
-__device__ __forceinline__ void atomic_add_f32(float* p, float v) {
-#ifdef HA_SIMT_EMU
-  atomicAdd(p, v);
-#else
-  unsafeAtomicAdd(p, v);
-#endif
-}
-
 // Zero-fill as a KERNEL (4-byte words).  Not hipMemsetAsync: inside a captured hipGraph a memset node followed by a kernel node was
 // observed (ROCm 7.0 / gfx950, round 4) to let the kernel start on the previous replay's contents -- the persistent roll-out kernel then
 // found its team counters already full (error word 0x100) -- while kernel -> kernel edges are ordered exactly as in a stream.

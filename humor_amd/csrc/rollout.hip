@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <list>
 #include <unordered_map>
 #include <vector>
 
@@ -45,15 +46,8 @@ typedef float vf4 __attribute__((ext_vector_type(4)));
 // (C % 4 == 0) is slab[rt * C * 32 + row * 4 + qoff(c)]
 __device__ __forceinline__ size_t qoff(int c) { return (size_t)(c >> 2) * 128 + (c & 3); }
 
-// layer-kernel launch policy picked up by ha_humor_net_create (ha_tune_set "layer_spb" / "layer_nw"; 0 = default)
-int g_layer_spb = 0, g_layer_nw = 0, g_layer_finish = 1;
-int g_layer_hsum = 1;  // summed pre-activation write-back for the adjoint (ha_tune_set "layer_hsum")
-// ha_tune_set "layer_acc" (experiment, default off): one-row-tile policy only.  1: the K-split blocks of a decoder layer ADD their
-// partial tiles into ONE pre-zeroed slab with hardware fp32 atomics (global_atomic_add_f32) instead of writing nsplit partial
-// slabs, so that every consumer block reads one slab instead of up to five.  Measured (profiles/experiments/README.md, round 2):
-// the consumers' load phase shrinks by 2-3 k cycles as predicted, but 1024 atomics per block drain in 2.5-5 k cycles and delay the
-// next launch: 32x59 fwd+bwd 4.55 -> 4.43 ms only, and the sum order of the partials (hence the last bit) varies run to run.
-int g_layer_acc = 0;
+// ha_tune_set "layer_finish": GroupNorm prologues in a finishing pass (gn_finish_kernel) -- 1 (default) from two row tiles on, 0 never, 2 always
+int g_layer_finish = 1;
 int g_gemm_rm = 0;    // row tiles per wave of the batched prior GEMM (ha_tune_set "gemm_rm"; 0 = by size)
 // ha_tune_set "gemm_ks" (default 2): two waves share a tile pair, each walks half of K, partial tiles summed through LDS before the
 // epilogue -- for GEMMs that leave most SIMDs idle (VPoser: 1920 x 512 x 512 is 480 waves on 1024 SIMDs, a frame-0 decode 16 waves:
@@ -83,6 +77,21 @@ int g_rollout_pipe_bwd = 1;
 // out and the failure path (NaN results, host-mapped error word, fall-back to the launch chain) can be exercised on a healthy GPU
 int g_rollout_persist_inject = 0;
 
+// The path of one roll-out call (the mode recorded with its stash): 0 = the launch chain; 1 = one persistent launch per direction, the
+// stash also carries the launch-chain slabs (either adjoint can read it); 2 = the same without them (a third of the forward's stores):
+// only the one-launch adjoint can read such a stash.
+enum class Path : int { chain = 0, one_launch = 1, one_launch_lean = 2 };
+
+// How one roll-out call runs, decided once by rollout_plan (forward) and kept with the stash it fills, so that every phase of the call
+// and the backward over that stash follow the same decision whatever the knobs or the persistent path's error word say by then.
+struct CallPlan {
+  Path path = Path::chain;
+  bool piped = false;          // on the persistent kernels with B > 32: chunks of <= 256 sequences one after another on the caller's stream
+  int ngroups = 1, rows_per_group = 0;
+  size_t group_floats = 0;     // stash stride between row groups (0 with one group)
+  const float* g_z_add = nullptr;   // backward only: the dL/dz addend, when the one-launch adjoint adds it in its final reduction
+};
+
 struct PackedLayer {
   int Cin = 0, skip = 0, Nout = 0;
   int nslices_f = 0, main_slices = 0, ntiles_f = 0, Nout_pad = 0;
@@ -104,11 +113,13 @@ struct ha_humor_net {
   bool delta = true;                       // the decoder emits residuals (HumorModel(output_delta=True)); ha_humor_net_set_option("output_delta")
   ha::PackedLayer dec[ha::MAXL], pri[ha::MAXL];
   ha::PersistNet* persist = nullptr;      // register-stationary decoder for the persistent forward (null: shape / device not eligible)
-  // The stash layout of a call depends on whether the persistent kernels serve it, which in turn depends on mutable state (the tune
-  // knob, the asynchronous error word).  A forward call decides ONCE and records the decision for the stash it fills; every later
-  // phase of that call and the backward over the same stash use the recorded mode (one host thread per device: no lock).
-  struct StashRec { int mode, B, S, knobs; };
-  mutable std::unordered_map<const void*, StashRec> stash_mode;
+  // The plan of each forward call, keyed by the stash it filled, for the backward over that stash (one host thread per device: no lock).
+  // A forward overwrites the record of its address and makes it the newest; beyond MAX_STASH_RECS records the oldest go first.
+  // A backward leaves the record in place: a second backward over a retained graph finds it again.
+  struct StashRec { ha::CallPlan plan; int B, S, knobs; std::list<const void*>::iterator age; };
+  static constexpr size_t MAX_STASH_RECS = 65536;
+  mutable std::unordered_map<const void*, StashRec> stash_recs;
+  mutable std::list<const void*> stash_age;   // oldest first
 };
 
 namespace ha {
@@ -125,7 +136,6 @@ struct LayerTask {
   float* dst;                                       // [nsplit_dst][RT][Nout_pad][32]
   float* hsum_dst;                                  // mode 1: the summed pre-activations of the source go back as ONE slab [RT][Csrc][32] (or null)
   int spb, nsplit_dst;                              // K-slices per block, ceil(nslices / spb)
-  int acc;                                          // 1: all K-splits add into slab 0 of dst (pre-zeroed) with fp32 atomics
   int nblocks;                                      // ntiles * nsplit_dst * RT
 };
 
@@ -137,7 +147,8 @@ struct LayerLaunch {
   int RT;
 };
 
-constexpr int MAXSPLIT = 5;   // K-slices / NW never exceeds this for the supported layer widths (K <= 1280)
+constexpr int SPB = 4;        // K-slices per block of a layer launch
+constexpr int MAXSPLIT = 5;   // K-slices / SPB never exceeds this for the supported layer widths (K <= 1280)
 
 // sums `nsplit` (<= MAXSPLIT) partial slabs of element (channel c, row) of tile rt.  All loads are unconditional (clamped
 // slab index, zero weight beyond nsplit) so they issue back-to-back instead of one round trip per slab.
@@ -260,8 +271,8 @@ __device__ unsigned int g_layer_launches;
 
 // One block = (task, row tile rt, output tile, K-split ks): its NWT waves walk the block's `spb` consecutive 64-channel
 // K-slices (wave w takes slices w, w + NWT, ...), accumulate in registers, reduce across waves through LDS and write one
-// partial slab.  spb is the per-network policy (ha_tune_set "layer_spb"): few slices per block spread the fp32 MFMA work
-// (256 FLOP/clk/CU) over more CUs but make every consumer block re-read nsplit partial slabs; spb >= nslices is full-K.
+// partial slab.  spb = SPB: few slices per block spread the fp32 MFMA work (256 FLOP/clk/CU) over more CUs but make every
+// consumer block re-read nsplit partial slabs.
 // LEAN: every task is a plain GEMM on finished single slabs (behind gn_finish_kernel): no GroupNorm state and no partial-slab
 // staging -- 56 VGPRs instead of 338, a quarter of the operand bytes per block.
 template <int NWT, bool LEAN>
@@ -365,15 +376,8 @@ __global__ __launch_bounds__(NWT * 64) void mlp_layer_kernel(LayerLaunch L) {
       for (int e = 0; e < 4; ++e)
         if (n + e < T.Nout) o[e] += T.bias[n + e];
     }
-    if (!LEAN && T.acc) {
-      // accumulate policy: the slab was zeroed before the roll-out; returnless global_atomic_add_f32, complete at the kernel boundary
-      float* dst = T.dst + (size_t)rt * T.Nout_pad * 32 + (size_t)(n >> 2) * 128 + row * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) atomic_add_f32(dst + e, o[e]);
-    } else {
-      float* dst = T.dst + ((size_t)ks * L.RT + rt) * T.Nout_pad * 32 + (size_t)(n >> 2) * 128 + row * 4;
-      *reinterpret_cast<vf4*>(dst) = o;
-    }
+    float* dst = T.dst + ((size_t)ks * L.RT + rt) * T.Nout_pad * 32 + (size_t)(n >> 2) * 128 + row * 4;
+    *reinterpret_cast<vf4*>(dst) = o;
   }
   HA_TS(6, true);
   HA_TS(7, false);
@@ -1515,7 +1519,7 @@ static int pack_layer(PackedLayer& L, const float* W, const float* bias, const f
   L.Nin_pad = L.ntiles_b * 32;
 
   L.group = has_gn ? Cin / 16 : 0;
-  HA_REQUIRE(ceil_div(L.nslices_f, 4) <= MAXSPLIT && ceil_div(L.nslices_b, 4) <= MAXSPLIT, "layer %dx%d needs more than %d K-splits", Nout,
+  HA_REQUIRE(ceil_div(L.nslices_f, SPB) <= MAXSPLIT && ceil_div(L.nslices_b, SPB) <= MAXSPLIT, "layer %dx%d needs more than %d K-splits", Nout,
              Cin + skip, MAXSPLIT);
   const int Kin = Cin + skip;
   // forward pack [tile][slice][kp/4][lane][kp%4]: lane l of (tile, slice, kp) <-> W[n = tile*32 + (l&31)][k]
@@ -1575,9 +1579,7 @@ static int pack_mlp(PackedLayer* out, const ha_mlp_desc* d, const char* name) {
 // Offsets (in floats) into the caller-owned stash.
 struct StashLayout {
   int RT = 0;
-  // launch policy of the layer kernel for this batch size: K-slices per block and the resulting partial-slab counts
-  int spb = 4, nw = 4;
-  int nsf_pri[MAXL], nsf_dec[MAXL], nsb_dec[MAXL];
+  int nsf_pri[MAXL], nsf_dec[MAXL], nsb_dec[MAXL];   // partial-slab counts of the layer launches (SPB K-slices per block)
   size_t zT = 0, t2j = 0, per_step = 0, steps = 0;
   size_t xT = 0;                  // input states of all steps, contiguous: [(S+1)][RT][D_INP][32] (the batched prior's A operand)
   size_t off_G = 0;
@@ -1594,10 +1596,6 @@ struct StashLayout {
   size_t fin[1] = {0};         // finished-activation scratch of a launch's task (finishing-pass policy only)
   bool finish = false;
   bool hsum = false;             // forward launches write the summed pre-activations back (one-row-tile policy: no finishing pass)
-  // accumulate policy (g_layer_acc, one-row-tile policy): every decoder activation / adjoint is ONE slab that the K-split blocks add
-  // into.  The slabs must be zero before the chain starts, so the adjoint's scratch is kept per step too and both regions are
-  // cleared by one memset per pass ((S+1) x 0.36 MB forward, S x 0.4 MB backward at one row tile).
-  bool acc = false;
   // persistent forward (rollout_persist.hip): every decoder activation is ONE complete slab (bias included), written by the
   // persistent kernel; the adjoint reads it like a one-split partial slab
   bool single = false;
@@ -1606,21 +1604,17 @@ struct StashLayout {
   size_t off_gn[3] = {0, 0, 0}, off_gl = 0;   // single: per step GroupNorm statistics [16][32][2] x 3, glue record [32][32]
   size_t off_ht[3] = {0, 0, 0};               // single: per step the hidden pre-activations again, team layout [8][channel][4 rows]
   size_t dz_part = 0;            // single: partial dL/dz products of the persistent adjoint [S][31][32][48]
-  size_t bwd_set = 0;            // acc: floats per step of the adjoint scratch (bwd_dec[] are offsets of step 0's set); else 0
-  size_t bwd_begin = 0, bwd_floats = 0;
-  int rd_f(int i) const { return (acc || single) ? 1 : nsf_dec[i]; }     // partial slabs a consumer of decoder layer i's output reads
-  int rd_b(int i) const { return acc ? 1 : nsb_dec[i]; }
+  int rd_f(int i) const { return single ? 1 : nsf_dec[i]; }     // partial slabs a consumer of decoder layer i's output reads
   size_t total = 0;
 };
 
-// row groups of the call being served on this host thread (for_each_group): side-by-side groups run on their own streams, and two
-// persistent launches cannot share the chip (each needs one block on every CU), so the one-launch path serves single-group calls only
-static thread_local int tl_groups = 1;
-// -1: make_layout decides from the live state (workspace queries); 0 / 1: the mode decided at the entry point of the call being served
-static thread_local int tl_single_mode = -1;
-static thread_local const float* tl_gz_add = nullptr;   // ha_humor_rollout_backward_ex: addend of dL/dz (rows of the group being run)
+// Can one group of `rows` sequences run as one persistent launch: the B <= 32 kernels, or the pipelined ones for 32 < rows <= 256.
+// (Side-by-side row groups run on their own streams, and two persistent launches cannot share the chip -- each needs one block on
+// every CU -- so rollout_plan gives the one-launch path to single-group calls and to the pipelined chunks only.)
+static bool one_launch_fits(int rows) { return g_layer_finish != 2 && (rows <= 32 || (rows <= 256 && g_rollout_pipe != 0)); }
 
-static void make_layout(const ha_humor_net* net, int B, int S, StashLayout& L, bool allow_acc = true) {
+// The stash layout of one row group of B sequences on `path` (the sampling roll-out: always the chain).
+static void make_layout(const ha_humor_net* net, int B, int S, Path path, StashLayout& L) {
   L.RT = ceil_div(B, 32);
   const size_t RT = L.RT;
   // K is split over blocks of 4 slices (the fp32 MFMA rate is 256 FLOP/clk/CU: the work has to be spread over the chip).  At
@@ -1628,20 +1622,15 @@ static void make_layout(const ha_humor_net* net, int B, int S, StashLayout& L, b
   // launch is a latency chain); from two row tiles on a finishing pass does that once per activation (gn_finish_kernel) and
   // the layer kernel runs as a lean GEMM.  Measured with tools/rollout_ab.py (fwd+bwd ms, in-kernel vs finishing pass):
   // 32 rows 5.7 / 6.4, 64 rows 7.9 / 7.2, 96 rows 10.2 / 7.7, 128 rows 10.6 / 8.3, 256 rows x 119 steps 29.6 / 21.2.
-  L.spb = g_layer_spb >= 4 ? g_layer_spb : 4;      // MAXSPLIT partial slabs at most (checked against the layer widths at pack time)
-  L.nw = 4;
-  for (int i = 0; i < net->n_pri; ++i) L.nsf_pri[i] = ceil_div(net->pri[i].nslices_f, L.spb);
-  for (int i = 0; i < net->n_dec; ++i) { L.nsf_dec[i] = ceil_div(net->dec[i].nslices_f, L.spb); L.nsb_dec[i] = ceil_div(net->dec[i].nslices_b, L.spb); }
+  for (int i = 0; i < net->n_pri; ++i) L.nsf_pri[i] = ceil_div(net->pri[i].nslices_f, SPB);
+  for (int i = 0; i < net->n_dec; ++i) { L.nsf_dec[i] = ceil_div(net->dec[i].nslices_f, SPB); L.nsb_dec[i] = ceil_div(net->dec[i].nslices_b, SPB); }
   // GroupNorm prologues once per activation in gn_finish_kernel (see there and the policy note above)
   L.finish = (L.RT >= 2 && g_layer_finish != 0) || g_layer_finish == 2;     // 0: never, 2: always (A/B runs)
-  const bool want_single = tl_single_mode >= 0 ? tl_single_mode >= 1 : (g_rollout_persist != 0 && persist_usable(net->persist));
-  const bool may_single = allow_acc && !L.finish && B <= 32 && tl_groups == 1;
   // 32 < B <= 256: the pipelined persistent kernels; the launch-chain adjoint behind them keeps its finishing-pass policy (it reads the
   // forward's pre-activations as ONE complete slab per activation and row tile, like behind the B <= 32 kernel)
-  L.pipe = allow_acc && B > 32 && B <= 256 && tl_groups == 1 && g_rollout_pipe != 0 && g_layer_finish != 2 && want_single;
-  L.single = (may_single && want_single) || L.pipe;
-  L.acc = allow_acc && !L.finish && !L.single && g_layer_acc != 0;
-  L.hsum = !L.finish && !L.acc && !L.single && g_layer_hsum != 0;
+  L.single = path != Path::chain;
+  L.pipe = L.single && B > 32;
+  L.hsum = !L.finish && !L.single;
   size_t o = 0;
   auto take = [&](size_t n) { size_t r = o; o += (n + 63) / 64 * 64; return r; };
   L.zT = take((size_t)S * RT * ZD * 32);
@@ -1675,13 +1664,7 @@ static void make_layout(const ha_humor_net* net, int B, int S, StashLayout& L, b
   L.carry = take(RT * 32 * 16);
   L.g_dec_out = take(RT * net->dec[net->n_dec - 1].Nout_pad * 32);
   L.g_pri_out = take((size_t)S * RT * net->pri[net->n_pri - 1].Nout_pad * 32);   // prior-output adjoints of all steps
-  L.bwd_begin = o;
-  for (int i = 0; i < net->n_dec; ++i) L.bwd_dec[i] = take((size_t)L.rd_b(i) * RT * net->dec[i].Nin_pad * 32);
-  if (L.acc) {
-    L.bwd_set = o - L.bwd_begin;
-    take(L.bwd_set * (size_t)(S - 1));          // sets of steps 1 .. S-1 behind step 0's
-    L.bwd_floats = o - L.bwd_begin;
-  }
+  for (int i = 0; i < net->n_dec; ++i) L.bwd_dec[i] = take((size_t)L.nsb_dec[i] * RT * net->dec[i].Nin_pad * 32);
   if (L.finish)
     L.fin[0] = take(RT * 1280 * 32);     // widest operand: K <= 1280 (checked at pack time)
   if (L.single) {
@@ -1691,8 +1674,7 @@ static void make_layout(const ha_humor_net* net, int B, int S, StashLayout& L, b
   L.total = o;
 }
 
-static void fwd_task(LayerTask& T, const PackedLayer& L, const float* src, int nsplit_src, const float* skip, float* dst, int spb,
-                     int nsplit_dst) {
+static void fwd_task(LayerTask& T, const PackedLayer& L, const float* src, int nsplit_src, const float* skip, float* dst, int nsplit_dst) {
   memset(&T, 0, sizeof(T));
   T.Wp = L.Wf; T.bias = L.bias;
   T.ntiles = L.ntiles_f; T.nslices = L.nslices_f; T.main_slices = L.main_slices; T.Nout = L.Nout; T.Nout_pad = L.Nout_pad;
@@ -1702,18 +1684,15 @@ static void fwd_task(LayerTask& T, const PackedLayer& L, const float* src, int n
   T.gamma = L.gamma; T.beta = L.beta; T.group = L.group ? L.group : 64;
   T.inv_group = 1.0f / (float)T.group;
   T.dst = dst;
-  T.spb = spb; T.nsplit_dst = nsplit_dst;
+  T.spb = SPB; T.nsplit_dst = nsplit_dst;
   T.nblocks = L.ntiles_f * nsplit_dst;          // x RT in launch_layers
 }
-
-// accumulate policy: more than one K-split block per output tile -> they add into the (pre-zeroed) single slab
-static void set_acc(LayerTask& T, bool acc) { T.acc = acc && T.nsplit_dst > 1 ? 1 : 0; }
 
 // backward through layer L: A = dh (adjoint of L's raw output), output = adjoint of L's input activation slabs.
 // `Lnext_gn` describes the GroupNorm that follows L (i.e. the consumer layer's gamma/beta/group) when dh has to be
 // derived from the consumer's input-gradient slabs (mode 3); null when dh is given directly (mode 0).
 static void bwd_task(LayerTask& T, const PackedLayer& L, const float* dsrc, int nsplit_d, int dC, const PackedLayer* Lnext_gn,
-                     const float* hsrc, int nsplit_h, float* dst, int spb, int nsplit_dst) {
+                     const float* hsrc, int nsplit_h, float* dst, int nsplit_dst) {
   memset(&T, 0, sizeof(T));
   T.Wp = L.Wb; T.bias = nullptr;
   T.ntiles = L.ntiles_b; T.nslices = L.nslices_b; T.main_slices = L.nslices_b; T.Nout = L.Cin + L.skip; T.Nout_pad = L.Nin_pad;
@@ -1724,7 +1703,7 @@ static void bwd_task(LayerTask& T, const PackedLayer& L, const float* dsrc, int 
   T.inv_group = 1.0f / (float)T.group;
   T.hsrc = hsrc; T.nsplit_h = nsplit_h; T.Ch = L.Nout_pad;
   T.dst = dst;
-  T.spb = spb; T.nsplit_dst = nsplit_dst;
+  T.spb = SPB; T.nsplit_dst = nsplit_dst;
   T.nblocks = L.ntiles_b * nsplit_dst;
 }
 
@@ -1837,10 +1816,10 @@ static int prior_backward_batched(const ha_humor_net* net, const StashLayout& L,
 constexpr int MAX_GROUPS = 8;
 
 // rows per group (whole 32-row tiles) and the group count for a batch of B sequences
-// pipelined: the call runs on the pipelined persistent kernels -- chunks of up to 256 sequences one after another on the caller's stream
+// piped: the call runs on the pipelined persistent kernels -- chunks of up to 256 sequences one after another on the caller's stream
 // (a persistent launch owns every CU: nothing runs beside it)
-static void group_plan(int B, int& ngroups, int& rows_per_group, bool pipelined = false) {
-  if (pipelined) {
+static void group_plan(int B, bool piped, int& ngroups, int& rows_per_group) {
+  if (piped) {
     rows_per_group = 256;
     ngroups = ceil_div(B, 256);
     return;
@@ -1853,34 +1832,42 @@ static void group_plan(int B, int& ngroups, int& rows_per_group, bool pipelined 
   ngroups = ceil_div(B, rows_per_group);
 }
 
-static bool pipelined_call(int B, int mode) { return mode >= 1 && B > 32 && g_rollout_pipe != 0 && g_layer_finish != 2; }
-
 // the process-wide knobs the stash layout depends on, packed: a backward call checks that they are the ones its forward ran with
-static int layout_knobs() {
-  return (g_layer_spb & 0xff) | ((g_layer_finish & 3) << 8) | ((g_layer_acc & 1) << 10) | ((g_layer_hsum & 1) << 11) | ((g_rollout_pipe & 1) << 12) |
-         ((g_rollout_groups & 0xff) << 13);
-}
-// The adjoint of a stash filled by a one-launch forward: mode 2 (no launch-chain slabs) can only be read by the one-launch adjoint -- the
-// stash decides, whatever the adjoint knobs say by now; mode 1 (slabs present) follows the live knobs.
-static bool adjoint_persistent(const StashLayout& L, int mode) {
-  if (!L.single) return false;
-  if (mode == 2) return true;
-  return g_rollout_persist_bwd != 0 && (!L.pipe || g_rollout_pipe_bwd != 0);
+static int layout_knobs() { return (g_layer_finish & 3) | ((g_rollout_pipe & 1) << 2) | ((g_rollout_groups & 0xff) << 3); }
+
+// The stash one group of `rows` sequences needs on the launch chain (the sampling roll-out's too) or, when `may_one_launch` and it fits,
+// on the one-launch path: the larger of the two (the path may change between a workspace query and the call).
+static size_t group_stash_floats(const ha_humor_net* net, int rows, int S, bool may_one_launch) {
+  StashLayout L;
+  make_layout(net, rows, S, Path::chain, L);
+  size_t best = L.total;
+  if (may_one_launch && one_launch_fits(rows)) {
+    make_layout(net, rows, S, Path::one_launch, L);
+    best = std::max(best, L.total);
+  }
+  return best;
 }
 
-static size_t group_stash_floats(const ha_humor_net* net, int rows, int S) {
-  // the largest of: persistent mode, launch-chain mode, sampling roll-out (the mode may change between the query and the call)
-  const int saved = tl_single_mode;
-  size_t best = 0;
-  for (int mode = 0; mode < 2; ++mode) {
-    tl_single_mode = mode;
-    StashLayout L, Ls;
-    make_layout(net, rows, S, L);
-    make_layout(net, rows, S, Ls, false);
-    best = std::max(best, std::max(L.total, Ls.total));
+// The plan of a forward call from the live knobs and the persistent path's state.  The one-launch path serves B <= 32 in one launch
+// and B > 32 pipelined in chunks of 256 (the tail chunk may be <= 32: the B <= 32 kernels serve it).  Its stash drops the launch-chain
+// slabs (Path::one_launch_lean) when the one-launch adjoint is to follow.
+static CallPlan rollout_plan(const ha_humor_net* net, int B, int S) {
+  CallPlan p;
+  if (g_rollout_persist != 0 && persist_usable(net->persist) && one_launch_fits(std::min(B, 256))) {
+    p.piped = B > 32;
+    const bool lean = g_rollout_persist_bwd != 0 && (!p.piped || g_rollout_pipe_bwd != 0);
+    p.path = lean ? Path::one_launch_lean : Path::one_launch;
   }
-  tl_single_mode = saved;
-  return best;
+  group_plan(B, p.piped, p.ngroups, p.rows_per_group);
+  p.group_floats = p.ngroups > 1 ? group_stash_floats(net, p.rows_per_group, S, p.piped) : 0;
+  return p;
+}
+
+// The adjoint of a group of `rows` sequences: a lean stash can only be read by the one-launch adjoint -- the stash decides, whatever the
+// adjoint knobs say by now; a one-launch stash with slabs follows the live knobs; a launch-chain stash takes the launch-chain adjoint.
+static bool adjoint_one_launch(const CallPlan& p, int rows) {
+  if (p.path == Path::one_launch_lean) return true;
+  return p.path == Path::one_launch && g_rollout_persist_bwd != 0 && (rows <= 32 || g_rollout_pipe_bwd != 0);
 }
 
 }  // namespace ha
@@ -1962,8 +1949,9 @@ extern "C" int ha_humor_net_set_option(ha_humor_net* net, const char* key, int v
 // debugging build only (tools/build_variant.sh pdebug -DHA_PERSIST_DEBUG): stash offsets (floats) of the regions the persistent
 // kernels exchange, so that a script can read them back: [xT, steps, per_step, off_G, off_dec0..3, off_gn0..2, off_gl, dz_part, single]
 extern "C" int ha_debug_persist_layout(const ha_humor_net* net, int B, int S, int64_t* out) {
+  const CallPlan p = rollout_plan(net, B, S);
   StashLayout L;
-  make_layout(net, B, S, L);
+  make_layout(net, B, S, p.ngroups == 1 ? p.path : Path::chain, L);
   int64_t v[] = {(int64_t)L.xT, (int64_t)L.steps, (int64_t)L.per_step, (int64_t)L.off_G, (int64_t)L.off_dec[0], (int64_t)L.off_dec[1], (int64_t)L.off_dec[2],
                  (int64_t)L.off_dec[3], (int64_t)L.off_gn[0], (int64_t)L.off_gn[1], (int64_t)L.off_gn[2], (int64_t)L.off_gl, (int64_t)L.dz_part, L.single ? 1 : 0,
                  (int64_t)L.persist_ws};
@@ -1984,18 +1972,17 @@ extern "C" int ha_debug_layer_timing(unsigned long long* out /* [64][10] */, uns
 extern "C" int ha_humor_rollout_workspace(const ha_humor_net* net, int B, int S, int64_t* stash_floats) {
   HA_REQUIRE(net && stash_floats, "ha_humor_rollout_workspace: null argument");
   HA_REQUIRE(B >= 1 && S >= 1, "ha_humor_rollout_workspace: B and S must be >= 1");
-  // whole batch (sampling roll-out: one chain; its slabs never accumulate) or the row groups of forward / backward side by side
+  // the largest over every plan a call of B x S may get: the whole batch on either path (the sampling roll-out: the chain), the row
+  // groups of the launch chain side by side, the chunks of the pipelined kernels one after another
   int ng, rpg;
-  group_plan(B, ng, rpg);
-  const size_t whole = group_stash_floats(net, B, S);
-  tl_groups = ng;
-  size_t grouped = ng > 1 ? (size_t)ng * group_stash_floats(net, rpg, S) : 0;
-  tl_groups = 1;
-  if (B > 256) {       // chunks of the pipelined kernels, one after another
-    group_plan(B, ng, rpg, true);
-    grouped = std::max(grouped, (size_t)ng * group_stash_floats(net, rpg, S));
+  group_plan(B, false, ng, rpg);
+  size_t need = group_stash_floats(net, B, S, true);
+  if (ng > 1) need = std::max(need, (size_t)ng * group_stash_floats(net, rpg, S, false));
+  if (B > 256) {
+    group_plan(B, true, ng, rpg);
+    need = std::max(need, (size_t)ng * group_stash_floats(net, rpg, S, true));
   }
-  *stash_floats = (int64_t)(whole > grouped ? whole : grouped);
+  *stash_floats = (int64_t)need;
   return HA_OK;
 }
 
@@ -2004,10 +1991,40 @@ extern "C" int ha_humor_rollout_workspace(const ha_humor_net* net, int B, int S,
 // steps so that the groups' chains advance side by side on their streams.
 enum { PH_BEGIN = 0, PH_STEP = 1, PH_END = 2 };
 
-static int rollout_forward_impl(const ha_humor_net* net, int B, int S, const float* past_in0, const float* z_seq,
-                                float* world, float* prior_mu, float* prior_var, float* stash, hipStream_t st, int phase, int t) {
-  StashLayout L;
-  make_layout(net, B, S, L);
+// One decoder step t of the launch chain: the decoder layers on (x_t, z_t), then the forward glue (x_{t+1}, G_{t+1}, world outputs).
+// `g` arrives zeroed but for the caller's own glue fields (the sampling roll-out's prior outputs); `hsum`: the layer launches also write
+// the summed pre-activations back for the adjoint.
+static int chain_decoder_step(const ha_humor_net* net, const StashLayout& L, int B, int S, int t, float* stash, float* world, bool hsum,
+                              GlueParams& g, hipStream_t st) {
+  const int RT = L.RT, nd = net->n_dec;
+  float* sp = stash + L.steps + (size_t)t * L.per_step;
+  float* xT = stash + L.xT + (size_t)t * RT * D_INP * 32;
+  const float* zT = stash + L.zT + (size_t)t * RT * ZD * 32;
+  for (int l = 0; l < nd; ++l) {
+    LayerLaunch LL;
+    memset(&LL, 0, sizeof(LL));
+    LL.RT = RT;
+    const float* src = l == 0 ? xT : sp + L.off_dec[l - 1];
+    fwd_task(LL.t[LL.ntasks++], net->dec[l], src, l == 0 ? 1 : L.nsf_dec[l - 1], zT, sp + L.off_dec[l], L.nsf_dec[l]);
+    if (l > 0 && hsum) LL.t[0].hsum_dst = sp + L.off_hsum[l - 1];
+    int rc = launch_layers(LL, L, stash, st);
+    if (rc != HA_OK) return rc;
+  }
+  g.B = B; g.S = S; g.t = t; g.RT = RT;
+  g.xT = xT;
+  g.xT_next = xT + (size_t)RT * D_INP * 32;
+  g.dec_out = sp + L.off_dec[nd - 1]; g.dec_nsplit = L.nsf_dec[nd - 1]; g.dec_pad = net->dec[nd - 1].Nout_pad;
+  g.Gs = sp + L.off_G;
+  g.Gs_next = sp + L.per_step + L.off_G;
+  g.t2j = stash + L.t2j;
+  g.world = world;
+  launch_glue_fwd(net->rotw, net->delta, RT * 32, st, g);
+  HA_LAUNCH_CHECK();
+  return HA_OK;
+}
+
+static int rollout_forward_impl(const ha_humor_net* net, const CallPlan& plan, const StashLayout& L, int B, int S, const float* past_in0,
+                                const float* z_seq, float* world, float* prior_mu, float* prior_var, float* stash, hipStream_t st, int phase, int t) {
   const int RT = L.RT, rows = RT * 32;
   auto step_ptr = [&](int t) { return stash + L.steps + (size_t)t * L.per_step; };
   auto x_ptr = [&](int t) { return stash + L.xT + (size_t)t * RT * D_INP * 32; };
@@ -2023,7 +2040,7 @@ static int rollout_forward_impl(const ha_humor_net* net, int B, int S, const flo
       for (int l = 0; l < 3; ++l) { f.off_gn[l] = L.off_gn[l]; f.off_ht[l] = L.off_ht[l]; }
       f.off_gl = L.off_gl;
       for (int l = 0; l < 4; ++l) f.dec_pad[l] = net->dec[l].Nout_pad;
-      f.hidden_slabs = tl_single_mode != 2;
+      f.hidden_slabs = plan.path != Path::one_launch_lean;
       f.t2j = stash + L.t2j;
       f.ws = stash + L.persist_ws;
       return persist_forward(net->persist, f, ((g_rollout_persist >> 1) & 1) | (g_rollout_persist_inject ? 2 : 0), st);
@@ -2031,7 +2048,6 @@ static int rollout_forward_impl(const ha_humor_net* net, int B, int S, const flo
     if (phase == PH_STEP) return HA_OK;
   }
   if (phase == PH_BEGIN) {
-    if (L.acc) zero_async(stash + L.steps, (size_t)(S + 1) * L.per_step * sizeof(float), st);
     HA_LAUNCH(transpose_in_kernel, dim3(256), dim3(256), 0, st, z_seq, stash + L.zT, B, S, ZD, ZD, RT);
     HA_LAUNCH_CHECK();
     HA_LAUNCH(transpose_in_kernel, dim3(64), dim3(256), 0, st, past_in0, x_ptr(0), B, 1, D_IN, D_INP, RT);
@@ -2041,40 +2057,14 @@ static int rollout_forward_impl(const ha_humor_net* net, int B, int S, const flo
     return HA_OK;
   }
 
-  const bool with_prior = prior_mu != nullptr;
-  const int nd = net->n_dec, np = net->n_pri;
+  const int np = net->n_pri;
   // the recurrence: decoder layers + glue per step (the prior only consumes the states: it runs afterwards for all steps at once)
   if (phase == PH_STEP) {
-    float* sp = step_ptr(t);
-    const float* zT = stash + L.zT + (size_t)t * RT * ZD * 32;
-    for (int l = 0; l < nd; ++l) {
-      LayerLaunch LL;
-      memset(&LL, 0, sizeof(LL));
-      LL.RT = RT;
-      const PackedLayer& P = net->dec[l];
-      const float* src = l == 0 ? x_ptr(t) : sp + L.off_dec[l - 1];
-      fwd_task(LL.t[LL.ntasks++], P, src, l == 0 ? 1 : L.rd_f(l - 1), zT, sp + L.off_dec[l], L.spb, L.nsf_dec[l]);
-      set_acc(LL.t[0], L.acc);
-      if (l > 0 && L.hsum) LL.t[0].hsum_dst = sp + L.off_hsum[l - 1];
-      int rc = launch_layers(LL, L, stash, st);
-      if (rc != HA_OK) return rc;
-    }
     GlueParams g;
     memset(&g, 0, sizeof(g));
-    g.B = B; g.S = S; g.t = t; g.RT = RT;
-    g.xT = x_ptr(t);
-    g.xT_next = x_ptr(t + 1);
-    const PackedLayer& DL = net->dec[net->n_dec - 1];
-    g.dec_out = sp + L.off_dec[net->n_dec - 1]; g.dec_nsplit = L.rd_f(net->n_dec - 1); g.dec_pad = DL.Nout_pad;
-    g.Gs = sp + L.off_G;
-    g.Gs_next = step_ptr(t + 1) + L.off_G;
-    g.t2j = stash + L.t2j;
-    g.world = world;
-    launch_glue_fwd(net->rotw, net->delta, rows, st, g);
-    HA_LAUNCH_CHECK();
-    return HA_OK;
+    return chain_decoder_step(net, L, B, S, t, stash, world, L.hsum, g, st);
   }
-  if (with_prior) {
+  if (prior_mu) {
     int rc = prior_forward_batched(net, L, stash, S, st);
     if (rc != HA_OK) return rc;
     PriorIOParams q;
@@ -2096,60 +2086,39 @@ extern "C" int ha_humor_rollout_sample(const ha_humor_net* net, int B, int S, co
   DeviceGuard guard(net->device);
   hipStream_t st = (hipStream_t)stream;
   StashLayout L;
-  make_layout(net, B, S, L, false);
+  make_layout(net, B, S, Path::chain, L);       // sampling: always the launch chain, one group
   const int RT = L.RT, rows = RT * 32;
-  auto step_ptr = [&](int t) { return stash + L.steps + (size_t)t * L.per_step; };
-  auto x_ptr = [&](int t) { return stash + L.xT + (size_t)t * RT * D_INP * 32; };
-  HA_LAUNCH(transpose_in_kernel, dim3(64), dim3(256), 0, st, past_in0, x_ptr(0), B, 1, D_IN, D_INP, RT);
+  float* x0 = stash + L.xT;
+  HA_LAUNCH(transpose_in_kernel, dim3(64), dim3(256), 0, st, past_in0, x0, B, 1, D_IN, D_INP, RT);
   HA_LAUNCH_CHECK();
-  HA_LAUNCH(init_state_kernel, dim3(ceil_div(rows, 64)), dim3(64), 0, st, past_in0, step_ptr(0) + L.off_G, stash + L.t2j, B, rows);
+  HA_LAUNCH(init_state_kernel, dim3(ceil_div(rows, 64)), dim3(64), 0, st, past_in0, stash + L.steps + L.off_G, stash + L.t2j, B, rows);
   HA_LAUNCH_CHECK();
-  const PackedLayer& DL = net->dec[net->n_dec - 1];
-  const PackedLayer& PL = net->pri[net->n_pri - 1];
+  const int np = net->n_pri;
   for (int t = 0; t < S; ++t) {
-    float* sp = step_ptr(t);
-    float* zT = stash + L.zT + (size_t)t * RT * ZD * 32;
     // the latent of this step depends on the prior of this step: prior network first (on the recurrence here), then sample,
     // then the decoder
-    for (int l = 0; l < net->n_pri; ++l) {
+    for (int l = 0; l < np; ++l) {
       LayerLaunch LL;
       memset(&LL, 0, sizeof(LL));
       LL.RT = RT;
-      const float* src = l == 0 ? x_ptr(t) : stash + L.smp_pri[l - 1];
-      fwd_task(LL.t[LL.ntasks++], net->pri[l], src, l == 0 ? 1 : L.nsf_pri[l - 1], nullptr, stash + L.smp_pri[l], L.spb, L.nsf_pri[l]);
+      const float* src = l == 0 ? x0 + (size_t)t * RT * D_INP * 32 : stash + L.smp_pri[l - 1];
+      fwd_task(LL.t[LL.ntasks++], net->pri[l], src, l == 0 ? 1 : L.nsf_pri[l - 1], nullptr, stash + L.smp_pri[l], L.nsf_pri[l]);
       int rc = launch_layers(LL, L, stash, st);
       if (rc != HA_OK) return rc;
     }
     SampleParams sp_;
     memset(&sp_, 0, sizeof(sp_));
     sp_.B = B; sp_.S = S; sp_.t = t; sp_.RT = RT;
-    sp_.pri_out = stash + L.smp_pri[net->n_pri - 1]; sp_.pri_nsplit = L.nsf_pri[net->n_pri - 1]; sp_.pri_pad = PL.Nout_pad;
-    sp_.eps = eps_seq; sp_.zT_t = zT; sp_.z_out = z_out;
+    sp_.pri_out = stash + L.smp_pri[np - 1]; sp_.pri_nsplit = L.nsf_pri[np - 1]; sp_.pri_pad = net->pri[np - 1].Nout_pad;
+    sp_.eps = eps_seq; sp_.zT_t = stash + L.zT + (size_t)t * RT * ZD * 32; sp_.z_out = z_out;
     HA_LAUNCH(sample_z_kernel, dim3(rows), dim3(64), 0, st, sp_);
     HA_LAUNCH_CHECK();
-    for (int l = 0; l < net->n_dec; ++l) {
-      LayerLaunch LL;
-      memset(&LL, 0, sizeof(LL));
-      LL.RT = RT;
-      const float* src = l == 0 ? x_ptr(t) : sp + L.off_dec[l - 1];
-      fwd_task(LL.t[LL.ntasks++], net->dec[l], src, l == 0 ? 1 : L.nsf_dec[l - 1], zT, sp + L.off_dec[l], L.spb, L.nsf_dec[l]);
-      int rc = launch_layers(LL, L, stash, st);
-      if (rc != HA_OK) return rc;
-    }
     GlueParams g;
     memset(&g, 0, sizeof(g));
-    g.B = B; g.S = S; g.t = t; g.RT = RT;
-    g.xT = x_ptr(t);
-    g.xT_next = x_ptr(t + 1);
-    g.dec_out = sp + L.off_dec[net->n_dec - 1]; g.dec_nsplit = L.nsf_dec[net->n_dec - 1]; g.dec_pad = DL.Nout_pad;
-    g.pri_out = stash + L.smp_pri[net->n_pri - 1]; g.pri_nsplit = L.nsf_pri[net->n_pri - 1]; g.pri_pad = PL.Nout_pad;
-    g.Gs = sp + L.off_G;
-    g.Gs_next = step_ptr(t + 1) + L.off_G;
-    g.t2j = stash + L.t2j;
-    g.world = world;
+    g.pri_out = sp_.pri_out; g.pri_nsplit = sp_.pri_nsplit; g.pri_pad = sp_.pri_pad;
     g.prior_mu = prior_mu; g.prior_var = prior_var;
-    launch_glue_fwd(net->rotw, net->delta, rows, st, g);
-    HA_LAUNCH_CHECK();
+    int rc = chain_decoder_step(net, L, B, S, t, stash, world, false, g, st);
+    if (rc != HA_OK) return rc;
   }
   return HA_OK;
 }
@@ -2170,11 +2139,9 @@ static int prior_adjoint_all(const ha_humor_net* net, const StashLayout& L, int 
   return prior_backward_batched(net, L, stash, S, st);
 }
 
-static int rollout_backward_impl(const ha_humor_net* net, int B, int S, const float* g_world,
+static int rollout_backward_impl(const ha_humor_net* net, const CallPlan& plan, const StashLayout& L, int B, int S, const float* g_world,
                                  const float* g_prior_mu, const float* g_prior_var, float* stash, float* g_past_in0,
                                  float* g_z_seq, hipStream_t st, int phase, int t) {
-  StashLayout L;
-  make_layout(net, B, S, L);
   const int RT = L.RT, rows = RT * 32;
   auto step_ptr = [&](int t) { return stash + L.steps + (size_t)t * L.per_step; };
   auto x_ptr = [&](int t) { return stash + L.xT + (size_t)t * RT * D_INP * 32; };
@@ -2182,9 +2149,7 @@ static int rollout_backward_impl(const ha_humor_net* net, int B, int S, const fl
   const PackedLayer& DL = net->dec[net->n_dec - 1];
   const int nd = net->n_dec;
   const int gxp_pad = net->pri[0].Nin_pad;
-  // adjoint scratch of decoder layer l at step t (accumulate policy: one pre-zeroed set per step; else one set reused by every step)
-  auto bd = [&](int l, int t) { return stash + L.bwd_dec[l] + (size_t)(t < 0 ? 0 : (t >= S ? S - 1 : t)) * L.bwd_set; };
-  if (L.acc && phase == PH_BEGIN) zero_async(stash + L.bwd_begin, L.bwd_floats * sizeof(float), st);
+  auto bd = [&](int l) { return stash + L.bwd_dec[l]; };     // adjoint scratch of decoder layer l (one set, reused by every step)
 
   // the prior's contribution to dL/dx_t for every step, before the reverse scan (it does not depend on the scan)
   if (with_prior && phase == PH_BEGIN) {
@@ -2202,13 +2167,13 @@ static int rollout_backward_impl(const ha_humor_net* net, int B, int S, const fl
     // step t+1 products (consumed when t < S-1)
     g.gx_dir_in = stash + L.gx_dir[(t + 1) & 1];
     g.gx_dir_out = stash + L.gx_dir[t & 1];
-    g.gxp_dec = bd(0, t + 1); g.gxp_dec_nsplit = L.rd_b(0); g.gxp_dec_pad = net->dec[0].Nin_pad;
+    g.gxp_dec = bd(0); g.gxp_dec_nsplit = L.nsb_dec[0]; g.gxp_dec_pad = net->dec[0].Nin_pad;
     if (with_prior && t + 1 < S) {
       g.gxp_pri = stash + L.gx_pri + (size_t)(t + 1) * RT * gxp_pad * 32; g.gxp_pri_nsplit = 1; g.gxp_pri_pad = gxp_pad;
     }
     g.dz_n = net->n_dec;
     for (int i = 0; i < net->n_dec; ++i) {
-      g.dz_src[i] = bd(i, t + 1); g.dz_nsplit[i] = L.rd_b(i); g.dz_pad[i] = net->dec[i].Nin_pad;
+      g.dz_src[i] = bd(i); g.dz_nsplit[i] = L.nsb_dec[i]; g.dz_pad[i] = net->dec[i].Nin_pad;
       g.dz_off[i] = net->dec[i].Cin;
     }
     if (t >= 0) {
@@ -2222,12 +2187,7 @@ static int rollout_backward_impl(const ha_humor_net* net, int B, int S, const fl
     }
   };
 
-  const bool persist_bwd = adjoint_persistent(L, tl_single_mode);
-  HA_REQUIRE(!(tl_single_mode == 2 && !(L.single && persist_usable(net->persist))),
-             "ha_humor_rollout_backward: this stash was filled by a persistent / pipelined forward without launch-chain slabs (only the one-launch "
-             "adjoint can read it) and the persistent path has been disabled since (a launch reported a failure, error word 0x%x): repeat the "
-             "forward call -- it will run on the launch chain", persist_error_word(net->persist));
-  if (persist_bwd) {
+  if (adjoint_one_launch(plan, B)) {
     if (phase == PH_BEGIN) {
       PersistBwd f;
       f.B = B; f.S = S;
@@ -2239,7 +2199,7 @@ static int rollout_backward_impl(const ha_humor_net* net, int B, int S, const fl
       f.off_gl = L.off_gl;
       for (int l = 0; l < 4; ++l) f.dec_pad[l] = net->dec[l].Nout_pad;
       f.t2j = stash + L.t2j;
-      f.g_past0 = g_past_in0; f.g_z = g_z_seq; f.g_z_add = tl_gz_add;
+      f.g_past0 = g_past_in0; f.g_z = g_z_seq; f.g_z_add = plan.g_z_add;
       f.dz_part = stash + L.dz_part;
       f.ws = stash + L.persist_ws;
       return persist_backward(net->persist, f, (g_rollout_persist >> 1) & 1, st);
@@ -2259,14 +2219,13 @@ static int rollout_backward_impl(const ha_humor_net* net, int B, int S, const fl
       LL.RT = RT;
       const PackedLayer& P = net->dec[l];
       if (l == nd - 1)
-        bwd_task(LL.t[LL.ntasks++], P, stash + L.g_dec_out, 1, P.Nout_pad, nullptr, nullptr, 0, bd(l, t), L.spb, L.nsb_dec[l]);
+        bwd_task(LL.t[LL.ntasks++], P, stash + L.g_dec_out, 1, P.Nout_pad, nullptr, nullptr, 0, bd(l), L.nsb_dec[l]);
       else if (L.hsum && L.nsf_dec[l] > 1)      // the forward pass left the summed pre-activations of layer l as one slab
-        bwd_task(LL.t[LL.ntasks++], P, bd(l + 1, t), L.rd_b(l + 1), net->dec[l + 1].Nin_pad, &net->dec[l + 1],
-                 sp + L.off_hsum[l], 1, bd(l, t), L.spb, L.nsb_dec[l]);
+        bwd_task(LL.t[LL.ntasks++], P, bd(l + 1), L.nsb_dec[l + 1], net->dec[l + 1].Nin_pad, &net->dec[l + 1],
+                 sp + L.off_hsum[l], 1, bd(l), L.nsb_dec[l]);
       else
-        bwd_task(LL.t[LL.ntasks++], P, bd(l + 1, t), L.rd_b(l + 1), net->dec[l + 1].Nin_pad, &net->dec[l + 1],
-                 sp + L.off_dec[l], L.rd_f(l), bd(l, t), L.spb, L.nsb_dec[l]);
-      set_acc(LL.t[0], L.acc);
+        bwd_task(LL.t[LL.ntasks++], P, bd(l + 1), L.nsb_dec[l + 1], net->dec[l + 1].Nin_pad, &net->dec[l + 1],
+                 sp + L.off_dec[l], L.rd_f(l), bd(l), L.nsb_dec[l]);
       int rc = launch_layers(LL, L, stash, st);
       if (rc != HA_OK) return rc;
     }
@@ -2305,38 +2264,40 @@ static int side_pool(int device, SidePool** out) {
   return HA_OK;
 }
 
-// runs fn(group, first row, rows, stream, phase, t) over every group and phase: group 0 on the caller's stream, the others on side
-// streams that wait for everything already queued on the caller's stream and are joined back into it.  The steps are issued
-// round-robin over the groups (the host issues ~3 us per launch, a chain advances one launch per ~6 us: issuing one group's
-// whole chain first would leave the others waiting for the host).
+// runs fn(group, first row, rows, layout, stream, phase, t) over every row group of the plan and phase: group 0 on the caller's stream,
+// the others on side streams that wait for everything already queued on the caller's stream and are joined back into it.  The steps
+// are issued round-robin over the groups (the host issues ~3 us per launch, a chain advances one launch per ~6 us: issuing one group's
+// whole chain first would leave the others waiting for the host).  Each group's stash layout is made once per call.
 template <typename F>
-static int for_each_group(int device, int B, int S, bool reverse, hipStream_t st, bool pipelined, F&& fn) {
-  int ng, rpg;
-  group_plan(B, ng, rpg, pipelined);
-  if (pipelined) {
+static int for_each_group(const ha_humor_net* net, const CallPlan& plan, int B, int S, bool reverse, hipStream_t st, F&& fn) {
+  const int ng = plan.ngroups, rpg = plan.rows_per_group;
+  auto rows_of = [&](int g) { return std::min(B - g * rpg, rpg); };
+  if (plan.piped) {
     // one persistent launch (per direction) per chunk of <= 256 sequences, in stream order
     for (int g = 0; g < ng; ++g) {
-      const int r0 = g * rpg, rows = (B - r0) < rpg ? (B - r0) : rpg;
-      int rc = fn(g, r0, rows, st, PH_BEGIN, 0);
+      const int r0 = g * rpg, rows = rows_of(g);
+      StashLayout L;
+      make_layout(net, rows, S, plan.path, L);
+      int rc = fn(g, r0, rows, L, st, PH_BEGIN, 0);
       // (the step phases are no-ops behind a persistent launch; the launch-chain adjoint behind a pipelined forward walks them)
-      for (int i = 0; i < S && rc == HA_OK; ++i) rc = fn(g, r0, rows, st, PH_STEP, reverse ? S - 1 - i : i);
-      if (rc == HA_OK) rc = fn(g, r0, rows, st, PH_END, 0);
+      for (int i = 0; i < S && rc == HA_OK; ++i) rc = fn(g, r0, rows, L, st, PH_STEP, reverse ? S - 1 - i : i);
+      if (rc == HA_OK) rc = fn(g, r0, rows, L, st, PH_END, 0);
       if (rc != HA_OK) return rc;
     }
     return HA_OK;
   }
-  struct GroupScope { int prev; explicit GroupScope(int n) : prev(tl_groups) { tl_groups = n; } ~GroupScope() { tl_groups = prev; } } scope(ng);
+  StashLayout L[MAX_GROUPS];
+  for (int g = 0; g < ng; ++g) make_layout(net, rows_of(g), S, plan.path, L[g]);
   SidePool* P = nullptr;
   if (ng > 1) {
-    int rc = side_pool(device, &P);
+    int rc = side_pool(net->device, &P);
     if (rc != HA_OK) return rc;
     HA_CHECK_HIP(hipEventRecord(P->fork, st));
     for (int g = 1; g < ng; ++g) HA_CHECK_HIP(hipStreamWaitEvent(P->stream[g], P->fork, 0));
   }
   auto run = [&](int phase, int t) {
     for (int g = 0; g < ng; ++g) {
-      const int r0 = g * rpg, rows = ng == 1 ? B : ((B - r0) < rpg ? (B - r0) : rpg);
-      const int rc = fn(g, r0, rows, g == 0 ? st : P->stream[g], phase, t);
+      const int rc = fn(g, g * rpg, rows_of(g), L[g], g == 0 ? st : P->stream[g], phase, t);
       if (rc != HA_OK) return rc;
     }
     return (int)HA_OK;
@@ -2366,33 +2327,25 @@ extern "C" int ha_humor_rollout_forward(const ha_humor_net* net, int B, int S, c
     return HA_ERR_HIP;
   }
   DeviceGuard guard(net->device);
-  // the roll-out mode of this call, decided once (see ha_humor_net::stash_mode)
-  int mode = (g_rollout_persist != 0 && persist_usable(net->persist)) ? 1 : 0;
-  const bool piped = pipelined_call(B, mode);
-  // mode 2: a pipelined forward whose adjoint will be the pipelined launch too writes the hidden pre-activations in the teams' layout only
-  // (no launch-chain slabs: a third of its stores); only the pipelined adjoint can read such a stash, and the backward entry checks that
-  // (the same for the B <= 32 kernels)
-  if (piped && g_rollout_persist_bwd != 0 && g_rollout_pipe_bwd != 0) mode = 2;
-  if (!piped && mode == 1 && B <= 32 && g_layer_finish != 2 && g_rollout_persist_bwd != 0) mode = 2;
-  int ng, rpg;
-  group_plan(B, ng, rpg, piped);
-  tl_groups = piped ? 1 : ng;
-  const size_t gs = ng > 1 ? group_stash_floats(net, rpg, S) : 0;
-  tl_groups = 1;
-  // (one entry per distinct stash address ever seen -- the allocator recycles them, a forward overwrites its entry -- so the map stays
-  // small; the wholesale clear is a backstop that a process would need 64 k live stashes to reach)
-  if (net->stash_mode.size() > 65536) net->stash_mode.clear();
-  net->stash_mode[stash] = ha_humor_net::StashRec{mode, B, S, layout_knobs()};
-  tl_single_mode = mode;
-  int rc;
-  rc = for_each_group(net->device, B, S, false, (hipStream_t)stream, piped, [&](int g, int r0, int rows, hipStream_t st, int phase, int t) {
+  const CallPlan plan = rollout_plan(net, B, S);
+  // record the plan for the backward over this stash (see ha_humor_net::stash_recs)
+  auto it = net->stash_recs.find(stash);
+  if (it != net->stash_recs.end()) net->stash_age.splice(net->stash_age.end(), net->stash_age, it->second.age);
+  else {
+    if (net->stash_recs.size() >= ha_humor_net::MAX_STASH_RECS) {
+      net->stash_recs.erase(net->stash_age.front());
+      net->stash_age.pop_front();
+    }
+    it = net->stash_recs.emplace(stash, ha_humor_net::StashRec{}).first;
+    it->second.age = net->stash_age.insert(net->stash_age.end(), stash);
+  }
+  it->second.plan = plan; it->second.B = B; it->second.S = S; it->second.knobs = layout_knobs();
+  return for_each_group(net, plan, B, S, false, (hipStream_t)stream, [&](int g, int r0, int rows, const StashLayout& L, hipStream_t st, int phase, int t) {
     const size_t r = (size_t)r0;
-    return rollout_forward_impl(net, rows, S, past_in0 + r * D_IN, z_seq + r * S * ZD, world + r * S * D_STATE,
+    return rollout_forward_impl(net, plan, L, rows, S, past_in0 + r * D_IN, z_seq + r * S * ZD, world + r * S * D_STATE,
                                 prior_mu ? prior_mu + r * S * ZD : nullptr, prior_var ? prior_var + r * S * ZD : nullptr,
-                                stash + (size_t)g * gs, st, phase, t);
+                                stash + (size_t)g * plan.group_floats, st, phase, t);
   });
-  tl_single_mode = -1;
-  return rc;
 }
 
 // dst[i] += src[i] (the launch-chain path of ha_humor_rollout_backward_ex; the persistent path adds in its final reduction)
@@ -2419,37 +2372,27 @@ extern "C" int ha_humor_rollout_backward_ex(const ha_humor_net* net, int B, int 
     return HA_ERR_HIP;
   }
   DeviceGuard guard(net->device);
-  // the mode the forward over this stash recorded (a stash this library has not seen: decided from the live state, as before)
-  const auto it = net->stash_mode.find(stash);
-  HA_REQUIRE(it != net->stash_mode.end(), "ha_humor_rollout_backward: no forward call of this network has filled this stash");
+  // the plan the forward over this stash recorded
+  const auto it = net->stash_recs.find(stash);
+  HA_REQUIRE(it != net->stash_recs.end(), "ha_humor_rollout_backward: no forward call of this network has filled this stash");
   HA_REQUIRE(it->second.B == B && it->second.S == S, "ha_humor_rollout_backward: the stash was filled by a forward call of %d x %d, not %d x %d",
              it->second.B, it->second.S, B, S);
-  HA_REQUIRE(it->second.knobs == layout_knobs(), "ha_humor_rollout_backward: a layout knob (layer_spb / layer_finish / layer_acc / layer_hsum / "
-             "rollout_pipe / rollout_groups) changed between the forward call that filled this stash and its backward");
-  tl_single_mode = it->second.mode;
-  const bool piped = pipelined_call(B, tl_single_mode >= 0 ? tl_single_mode : ((g_rollout_persist != 0 && persist_usable(net->persist)) ? 1 : 0));
-  int ng, rpg;
-  group_plan(B, ng, rpg, piped);
-  tl_groups = piped ? 1 : ng;
-  const size_t gs = ng > 1 ? group_stash_floats(net, rpg, S) : 0;
-  tl_groups = 1;
-  int rc;
-  bool add_in_kernel = false;
-  if (g_z_add && tl_single_mode >= 1 && ng == 1) {
-    StashLayout L;
-    make_layout(net, B, S, L);
-    add_in_kernel = adjoint_persistent(L, tl_single_mode);
-  }
-  tl_gz_add = add_in_kernel ? g_z_add : nullptr;
-  rc = for_each_group(net->device, B, S, true, (hipStream_t)stream, piped, [&](int g, int r0, int rows, hipStream_t st, int phase, int t) {
+  HA_REQUIRE(it->second.knobs == layout_knobs(), "ha_humor_rollout_backward: a layout knob (layer_finish / rollout_pipe / rollout_groups) changed "
+             "between the forward call that filled this stash and its backward");
+  CallPlan plan = it->second.plan;
+  HA_REQUIRE(plan.path != Path::one_launch_lean || persist_usable(net->persist),
+             "ha_humor_rollout_backward: this stash was filled by a persistent / pipelined forward without launch-chain slabs (only the one-launch "
+             "adjoint can read it) and the persistent path has been disabled since (a launch reported a failure, error word 0x%x): repeat the "
+             "forward call -- it will run on the launch chain", persist_error_word(net->persist));
+  // dL/dz += g_z_add: in the one-launch adjoint's final reduction when it serves the whole call, else add_inplace_kernel afterwards
+  if (g_z_add && plan.ngroups == 1 && adjoint_one_launch(plan, B)) plan.g_z_add = g_z_add;
+  const int rc = for_each_group(net, plan, B, S, true, (hipStream_t)stream, [&](int g, int r0, int rows, const StashLayout& L, hipStream_t st, int phase, int t) {
     const size_t r = (size_t)r0;
-    return rollout_backward_impl(net, rows, S, g_world ? g_world + r * S * D_STATE : nullptr,
+    return rollout_backward_impl(net, plan, L, rows, S, g_world ? g_world + r * S * D_STATE : nullptr,
                                  g_prior_mu ? g_prior_mu + r * S * ZD : nullptr, g_prior_var ? g_prior_var + r * S * ZD : nullptr,
-                                 stash + (size_t)g * gs, g_past_in0 + r * D_IN, g_z_seq + r * S * ZD, st, phase, t);
+                                 stash + (size_t)g * plan.group_floats, g_past_in0 + r * D_IN, g_z_seq + r * S * ZD, st, phase, t);
   });
-  tl_single_mode = -1;
-  tl_gz_add = nullptr;
-  if (rc == HA_OK && g_z_add && !add_in_kernel) {
+  if (rc == HA_OK && g_z_add && !plan.g_z_add) {
     const int n = B * S * ZD;
     HA_LAUNCH(add_inplace_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, g_z_seq, g_z_add, n);
     HA_LAUNCH_CHECK();

@@ -46,7 +46,7 @@ int g_skin_variant = -1;
 int g_dense_gA_sparse = 2;   // ha_tune_set("dense_gA_sparse"): dL/dA of the dense backward -- 2 (default) = MFMA product over the joints each 64-vertex
                              // chunk touches (205 us at N = 1920), 1 = by joint lists (255 us), 0 = dense 64-column MFMA product (417 us)
 int g_dense_bwd_waves = 0;   // ha_tune_set("dense_bwd_waves"): wave-count target of the dense backward's K split (0 = default)
-extern int g_layer_spb, g_layer_nw, g_layer_finish, g_gemm_rm, g_layer_hsum, g_layer_acc, g_rollout_groups, g_gemm_ks, g_rollout_persist, g_rollout_persist_bwd, g_rollout_persist_inject, g_rollout_pipe, g_rollout_pipe_bwd;   // rollout.hip
+extern int g_layer_finish, g_gemm_rm, g_rollout_groups, g_gemm_ks, g_rollout_persist, g_rollout_persist_bwd, g_rollout_persist_inject, g_rollout_pipe, g_rollout_pipe_bwd;   // rollout.hip
 extern unsigned g_cu_poison;   // debug.hip
 }
 extern "C" int ha_tune_set(const char* key, int value) {
@@ -54,12 +54,8 @@ extern "C" int ha_tune_set(const char* key, int value) {
   if (strcmp(key, "skin_variant") == 0) { ha::g_skin_variant = value; return HA_OK; }
   if (strcmp(key, "dense_bwd_waves") == 0) { ha::g_dense_bwd_waves = value; return HA_OK; }
   if (strcmp(key, "dense_gA_sparse") == 0) { ha::g_dense_gA_sparse = value; return HA_OK; }
-  if (strcmp(key, "layer_spb") == 0) { ha::g_layer_spb = value; return HA_OK; }
-  if (strcmp(key, "layer_nw") == 0) { ha::g_layer_nw = value; return HA_OK; }
   if (strcmp(key, "layer_finish") == 0) { ha::g_layer_finish = value; return HA_OK; }
   if (strcmp(key, "gemm_rm") == 0) { ha::g_gemm_rm = value; return HA_OK; }
-  if (strcmp(key, "layer_hsum") == 0) { ha::g_layer_hsum = value; return HA_OK; }
-  if (strcmp(key, "layer_acc") == 0) { ha::g_layer_acc = value; return HA_OK; }
   if (strcmp(key, "rollout_groups") == 0) { ha::g_rollout_groups = value; return HA_OK; }
   if (strcmp(key, "gemm_ks") == 0) { ha::g_gemm_ks = value; return HA_OK; }
   if (strcmp(key, "rollout_persist") == 0) { ha::g_rollout_persist = value; return HA_OK; }

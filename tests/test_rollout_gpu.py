@@ -25,13 +25,6 @@ def fwd_path(request, gpu_lib):
     gpu_lib.call('ha_tune_set', b'rollout_persist_bwd', 1)
 
 
-@pytest.fixture
-def chain_only(gpu_lib):
-    gpu_lib.call('ha_tune_set', b'rollout_persist', 0)
-    yield
-    gpu_lib.call('ha_tune_set', b'rollout_persist', 1)
-
-
 @pytest.mark.parametrize('B,S', [(1, 1), (2, 3), (4, 10), (32, 12), (33, 5), (70, 3), (130, 2)])   # 130 rows: full-K launch policy
 def test_rollout_forward_backward(gpu_lib, dev, fwd_path, B, S):
     """Flat bars (1e-4 on every state / prior output, 1e-3 of the largest entry on every gradient) on the random network.  A sequence whose
@@ -157,28 +150,6 @@ def test_rollout_determinism(gpu_lib, dev, fwd_path):
     a = RC.world_of(hm.roll_out(past, None, 20, z_seq=z))
     b = RC.world_of(hm.roll_out(past, None, 20, z_seq=z))
     assert torch.equal(a, b)
-
-
-def test_rollout_accumulate_policy(gpu_lib, dev, chain_only):
-    """ha_tune_set("layer_acc", 1) (fp32-atomic accumulation of the K-split partial tiles, off by default) against the fixed-order
-    partial-slab path: same values and gradients up to the summation order of <= 5 partials per element."""
-    hm, _ = RC.make_model(gpu_lib, dev, contractive=True)
-    g = torch.Generator().manual_seed(2)
-    past = RC.canonical_state(8, g).to(dev)
-    z = torch.randn(8, 20, 48, generator=g).to(dev)
-    res = []
-    try:
-        for acc in (0, 1, 1):
-            gpu_lib.call('ha_tune_set', b'layer_acc', acc)
-            p, zz = past.clone().requires_grad_(True), z.clone().requires_grad_(True)
-            out, (pm, pv) = hm.roll_out(p, None, 20, z_seq=zz, return_prior=True)
-            (out['joints'].square().sum() + pm.sum() + pv.sum()).backward()
-            res.append((RC.world_of(out).detach(), p.grad.clone(), zz.grad.clone()))
-    finally:
-        gpu_lib.call('ha_tune_set', b'layer_acc', 0)
-    for k in (1, 2):
-        for a, b in zip(res[0], res[k]):
-            assert (a - b).abs().max().item() <= 1e-5 * max(1.0, a.abs().max().item())
 
 
 @pytest.mark.parametrize('B,groups', [(70, 2), (70, 3), (130, 4)])

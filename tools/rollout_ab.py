@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""A/B of the roll-out layer-kernel launch policy (slices per block, waves per block): event-timed forward and
-forward+backward of HumorModel.roll_out.  usage: rollout_ab.py B S "spb,finish[,hsum[,acc]]" ...   (spb 0 = default; finish 0 off / 1 auto / 2 forced; hsum / acc 0 / 1)"""
+"""A/B of the roll-out launch-chain policy (GroupNorm finishing pass, row groups): event-timed forward and forward+backward of
+HumorModel.roll_out.  usage: rollout_ab.py B S "finish[,groups]" ...   (finish 0 off / 1 auto / 2 forced; groups 0 = auto)"""
 import os
 import sys
 
@@ -25,7 +25,7 @@ def timed(fn, iters):
 
 def main():
     B, S = int(sys.argv[1]), int(sys.argv[2])
-    cfgs = [tuple(int(x) for x in a.split(',')) for a in sys.argv[3:]] or [(4, 4)]
+    cfgs = [tuple(int(x) for x in a.split(',')) for a in sys.argv[3:]] or [(1,)]
     dev = torch.device('cuda:0')
     lib = _lib.get_lib()
     sd = synth.humor_state_dict(seed=0)
@@ -33,15 +33,10 @@ def main():
     z = torch.randn(B, S, 48, device=dev, requires_grad=True)
     ref = None
     for cfg in cfgs:
-        spb, nw = cfg[0], cfg[1]
-        hsum = cfg[2] if len(cfg) > 2 else 1                                       # third number: summed-h write-back (default on)
-        acc = cfg[3] if len(cfg) > 3 else 0                                        # fourth number: fp32-atomic accumulate policy (default off)
-        lib.call('ha_tune_set', b'layer_acc', acc)
-        groups = cfg[4] if len(cfg) > 4 else 0                                     # fifth number: row groups on side streams (0 = auto)
+        finish = cfg[0]
+        groups = cfg[1] if len(cfg) > 1 else 0                                     # second number: row groups on side streams (0 = auto)
         lib.call('ha_tune_set', b'rollout_groups', groups)
-        lib.call('ha_tune_set', b'layer_spb', spb)
-        lib.call('ha_tune_set', b'layer_finish', nw if nw in (0, 1, 2) else 1)   # second number: 0 off, 1 auto, 2 forced
-        lib.call('ha_tune_set', b'layer_hsum', hsum)
+        lib.call('ha_tune_set', b'layer_finish', finish)
         hm = HumorModel(in_rot_rep='mat', out_rot_rep='aa', model_data_config='smpl+joints+contacts')
         hm.load_state_dict(sd)
         hm = hm.to(dev).eval()
@@ -60,7 +55,7 @@ def main():
             ref = w
         it = 5 if B * S > 4000 else 10
         tf, tb = timed(fwd, it), timed(fwdbwd, it)
-        print(f'B={B} S={S} spb={spb} nw={nw} hsum={hsum} acc={acc} groups={groups}: fwd {tf:8.3f} ms  fwd+bwd {tb:8.3f} ms   max|joints - first cfg| (step<=8) '
+        print(f'B={B} S={S} finish={finish} groups={groups}: fwd {tf:8.3f} ms  fwd+bwd {tb:8.3f} ms   max|joints - first cfg| (step<=8) '
               f'{(w - ref).abs().max().item():.2e}', flush=True)
 
 
