@@ -49,9 +49,10 @@ __device__ __forceinline__ size_t qoff(int c) { return (size_t)(c >> 2) * 128 + 
 // ha_tune_set "layer_finish": GroupNorm prologues in a finishing pass (gn_finish_kernel) -- 1 (default) from two row tiles on, 0 never, 2 always
 int g_layer_finish = 1;
 int g_gemm_rm = 0;    // row tiles per wave of the batched prior GEMM (ha_tune_set "gemm_rm"; 0 = by size)
-// ha_tune_set "gemm_ks" (default 2): two waves share a tile pair, each walks half of K, partial tiles summed through LDS before the
-// epilogue -- for GEMMs that leave most SIMDs idle (VPoser: 1920 x 512 x 512 is 480 waves on 1024 SIMDs, a frame-0 decode 16 waves:
-// a launch is exactly one wave's serial MFMA chain).  0 = off, 3 = also for large GEMMs (measured slower: tools/gemm_ks_ab.py).
+// ha_tune_set "gemm_ks" (default 2): GEMMs that leave most SIMDs idle are cut into short MFMA chains -- up to four waves share a unit of
+// column tiles, each walks its share of K, the partial tiles are summed in part order through LDS before the epilogue; epilogues without
+// GroupNorm take one column tile per wave (plan_prior_gemm: a frame-0 VPoser decode is 16 waves in the plain form, the launch lasts exactly
+// one wave's serial chain).  0 = off (plain form everywhere), 3 = force the deepest split also for large GEMMs (measured slower).
 int g_gemm_ks = 2;
 // ha_tune_set "rollout_groups": 0 = auto, n >= 1 = split the batch into (at most) n row groups that run the chain side by side on
 // their own HIP streams (fork / join on the caller's stream with events; capturable), each with its own stash region and its steps
@@ -501,29 +502,33 @@ struct GemmTask {
 
 constexpr int GEMM_LDS_WAVE = 2 * 8 * 132;    // floats of epilogue staging per wave: [column tile][quad][32 rows x 4 + pad]
 
-// KS = 2: waves (2 cw, 2 cw + 1) of a block share tile pair cw of the block's two; wave kpart walks half of the K slices, the partial
-// tiles meet in LDS and the even wave runs the epilogue.
-template <int RM, int KS = 1>
+// KS = 2 / 4: KS adjacent waves of a block share one unit (TN column tiles) of the block's 4 / KS; wave kpart walks its share of the K slices,
+// the partial tiles meet in LDS and wave kpart = 0 adds them in part order (0 + 1 + .. + KS-1: the same bits on every run) and runs the epilogue.
+// TN = 1: a wave owns ONE 32-column tile (one accumulator, half the B registers) -- for the epilogues that need no complete GroupNorm
+// group inside the wave (0 / 4 / 5).  Every output element sees the same MFMAs in the same k order as in the pair form: TN changes no bit.
+template <int RM, int KS = 1, int TN = 2>
 __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
+  static_assert(KS == 1 || RM == 1, "the K split is built for one row tile per wave");
+  static_assert((KS == 1 || KS == 2 || KS == 4) && (TN == 1 || TN == 2), "prior_gemm_kernel: unsupported shape");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int w = (int)(blockIdx.x & 7) * T.per_xcd + (int)(blockIdx.x >> 3);
   if ((int)(blockIdx.x >> 3) >= T.per_xcd || w >= T.nwork) return;      // (block-uniform)
   const int cb = w / T.nrg, rg = w % T.nrg;
   const int kpart = KS == 1 ? 0 : wave % KS;
-  const int ct0 = KS == 1 ? (cb * 4 + wave) * 2 : (cb * (4 / KS) + wave / KS) * 2;
+  const int ct0 = KS == 1 ? (cb * 4 + wave) * TN : (cb * (4 / KS) + wave / KS) * TN;
   const bool tile_ok = ct0 < T.ntiles;
-  if (KS == 1 && !tile_ok) return;                           // (with a K split the idle waves stay for the block barriers)
-  const int ct1 = ct0 + 1 < T.ntiles ? ct0 + 1 : ct0;      // an odd last tile: the second accumulator is computed and dropped
+  if (KS == 1 && !tile_ok) return;                           // (with a K split the idle waves stay for the block barrier)
+  const int ct1 = TN == 2 && ct0 + 1 < T.ntiles ? ct0 + 1 : ct0;      // an odd last tile: the second accumulator is computed and dropped
   int rt[RM];
 #pragma unroll
   for (int m = 0; m < RM; ++m) rt[m] = rg * RM + m < T.nrt ? rg * RM + m : T.nrt - 1;
 
-  f32x16 acc[RM][2];
+  f32x16 acc[RM][TN];
 #pragma unroll
   for (int m = 0; m < RM; ++m)
 #pragma unroll
-    for (int c = 0; c < 2; ++c)
+    for (int c = 0; c < TN; ++c)
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[m][c][i] = 0.f;
 
@@ -533,9 +538,11 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const vf4 u = *reinterpret_cast<const vf4*>(wp0 + (size_t)slice * 2048 + j * 256);
-      const vf4 v = *reinterpret_cast<const vf4*>(wp1 + (size_t)slice * 2048 + j * 256);
       b0[4 * j] = u.x; b0[4 * j + 1] = u.y; b0[4 * j + 2] = u.z; b0[4 * j + 3] = u.w;
-      b1[4 * j] = v.x; b1[4 * j + 1] = v.y; b1[4 * j + 2] = v.z; b1[4 * j + 3] = v.w;
+      if (TN == 2) {      // (TN = 1: b1 is never read, its registers fold away)
+        const vf4 v = *reinterpret_cast<const vf4*>(wp1 + (size_t)slice * 2048 + j * 256);
+        b1[4 * j] = v.x; b1[4 * j + 1] = v.y; b1[4 * j + 2] = v.z; b1[4 * j + 3] = v.w;
+      }
     }
   };
   // full 64-channel slices: unconditional 16-byte loads (nothing depends on the loaded values before the MFMAs read them)
@@ -550,7 +557,7 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
 #pragma unroll
       for (int m = 0; m < RM; ++m) {
         acc[m][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][kp], b0[kp], acc[m][0], 0, 0, 0);
-        acc[m][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][kp], b1[kp], acc[m][1], 0, 0, 0);
+        if (TN == 2) acc[m][TN - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][kp], b1[kp], acc[m][TN - 1], 0, 0, 0);
       }
   };
   const int nfull_all = T.Csrc / SLICE < T.nslices ? T.Csrc / SLICE : T.nslices;      // slices whose 64 channels all exist in the slab
@@ -593,8 +600,9 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
   // ---- epilogue: accumulators -> (row, 32 channels of one column tile) per lane through the wave's LDS slice -----------------
   float* sl = smem + wave * GEMM_LDS_WAVE;
   const int row = lane & 31, hh = lane >> 5;
-  const int ct = hh ? ct0 + 1 : ct0;                  // this lane's column tile
-  const bool ct_ok = ct < T.ntiles;
+  const int ct = hh ? ct0 + 1 : ct0;                  // this lane's column tile (TN = 1: the upper half-wave has none)
+  const bool ct_ok = hh < TN && ct < T.ntiles;
+  const int hs = hh < TN ? hh : 0;                    // staged tile this lane reads
   float gam[32], bet[32];
   if ((T.epi == 1 || T.epi == 3) && ct_ok) {
 #pragma unroll
@@ -612,7 +620,7 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
   for (int m = 0; m < RM; ++m) {
     // accumulator register i of lane l: row (i&3) + 8 (i>>2) + 4 (l>>5), column l&31
 #pragma unroll
-    for (int c = 0; c < 2; ++c)
+    for (int c = 0; c < TN; ++c)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int r = (i & 3) + 8 * (i >> 2) + 4 * hh, col = lane & 31;
@@ -624,14 +632,15 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     } else {
       __syncthreads();                                  // the K partners' partial tiles are staged
+      if (kpart != 0) return;                           // only the first wave of the unit finishes the tile (RM = 1: no barrier below)
     }
     float v[32];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      vf4 q = *reinterpret_cast<const vf4*>(sl + (hh * 8 + j) * 132 + row * 4);
+      vf4 q = *reinterpret_cast<const vf4*>(sl + (hs * 8 + j) * 132 + row * 4);
       if (KS > 1) {
 #pragma unroll
-        for (int pk = 1; pk < KS; ++pk) q += *reinterpret_cast<const vf4*>(sl + pk * GEMM_LDS_WAVE + (hh * 8 + j) * 132 + row * 4);
+        for (int pk = 1; pk < KS; ++pk) q += *reinterpret_cast<const vf4*>(sl + pk * GEMM_LDS_WAVE + (hs * 8 + j) * 132 + row * 4);
       }
       v[4 * j] = q.x; v[4 * j + 1] = q.y; v[4 * j + 2] = q.z; v[4 * j + 3] = q.w;
     }
@@ -639,9 +648,6 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();                  // the slice is rewritten by the next row tile
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-      __syncthreads();
-      if (kpart != 0) continue;                         // only the even wave of the pair finishes the tile (no block barrier below)
     }
     const bool live = ct_ok && rg * RM + m < T.nrt;
     if (T.bias && ct_ok) {       // the packed bias is zero-padded to whole 32-column tiles
@@ -1742,23 +1748,66 @@ static int launch_layers(LayerLaunch& LL, const StashLayout& L, float* stash, hi
 }
 
 
+// Shape of one batched GEMM launch: RM row tiles x TN column tiles per unit, KS waves per unit, 4 / KS units per 256-thread block.
+struct GemmPlan { int rm, tn, ks, ncb; };
+
+// Which instantiation a launch takes.  A small launch (32 rows, or a layer with 96 columns) is ONE wave's serial MFMA chain on a mostly
+// idle machine: its duration is the chain length (slices per wave x 32 TN MFMAs of 64 cycles), not the work.  So below the size at which
+// the plain form already gives every SIMD its wave, the launch is shaped for the shortest time on the MFMA pipes,
+//   cost = ceil(waves / 1024 SIMDs) x slices per wave x TN            (waves that share a SIMD run their chains one after the other)
+// over TN = 1 where the epilogue needs no complete GroupNorm group in the wave (0 / 4 / 5) and KS in {1, 2, 4} with >= 2 slices left per
+// wave, at most two waves per SIMD (2048) in the launch.  Equal cost: the larger TN (half the A loads), then the smaller K split (less LDS
+// traffic, fewer reordered sums) -- 1888 x 1024 -> 339 stays at TN 2 / KS 2 (708 waves x 8 slices): four waves per pair are 1416 waves of
+// half the chain, two of them on 392 SIMDs, measured 31.8 us against 20.9.
+// Pinned: everything that takes RM = 2, and every launch the unsplit pair form runs with more than 512 waves (the square prior products,
+// the posterior encoder at 1888 rows, all C5-size launches) keeps exactly that form and grid.
+// ks_knob (ha_tune_set "gemm_ks"): 0 = no split and the pair form everywhere, 2 = the policy above, 3 = force the deepest split / TN = 1.
+static GemmPlan plan_prior_gemm(int ntiles, int nslices, int nrt, int epi, int rm_knob, int ks_knob) {
+  GemmPlan P;
+  P.ncb = ceil_div(ntiles, 8);
+  P.rm = rm_knob == 1 || rm_knob == 2 ? rm_knob : ((nrt / 2) * P.ncb >= 2 * 256 ? 2 : 1);
+  P.tn = 2;
+  P.ks = 1;
+  const bool split_on = ks_knob == 2 || ks_knob == 3;
+  if (!split_on || P.rm == 2) return P;
+  const bool force = ks_knob == 3;
+  if (!force && P.ncb * nrt * 4 > 512) return P;
+  const bool gn = epi == 1 || epi == 3;
+  constexpr int SIMDS = 1024;
+  int best = ceil_div(ceil_div(ntiles, 2) * nrt, SIMDS) * nslices * 2;      // the plain form (cost in units of 32 MFMAs)
+  if (force) best = nslices * 2;
+  for (int tn = 2; tn >= (gn ? 2 : 1); --tn)
+    for (int ks = 1; ks <= 4; ks *= 2) {
+      if (ks > 1 && nslices < 2 * ks) continue;
+      const int waves = ceil_div(ntiles, tn) * nrt * ks;
+      if (!force && waves > 2 * SIMDS) continue;
+      const int chain = ceil_div(nslices, ks) * tn;
+      const int cost = force ? chain : ceil_div(waves, SIMDS) * chain;
+      if (cost < best || (force && cost == best && ks > P.ks)) { best = cost; P.tn = tn; P.ks = ks; P.ncb = ceil_div(ntiles, tn * 4 / ks); }
+    }
+  return P;
+}
+
 // one batched prior layer (forward l >= 0 / adjoint) over nrt = S * RT row tiles
 static int launch_prior_gemm(GemmTask& T, hipStream_t st) {
   HA_REQUIRE((T.epi != 1 && T.epi != 3) || (T.ntiles % 2 == 0 && (T.group == 32 || T.group == 64)), "prior GEMM: GroupNorm epilogue needs whole 64-column pairs");
-  // RM = 2 (64 x 64 per wave) once there are enough row tiles to keep every SIMD busy with the larger tile
-  int ncb = ceil_div(T.ntiles, 8);
-  const int rm = g_gemm_rm == 1 || g_gemm_rm == 2 ? g_gemm_rm : ((T.nrt / 2) * ncb >= 2 * 256 ? 2 : 1);
-  // K split (experiment knob): only for the one-row-tile-per-wave form and GEMMs that leave most SIMDs idle
-  const int ks = ((g_gemm_ks == 2 || g_gemm_ks == 3) && rm == 1 && T.nslices >= 4 && (g_gemm_ks == 3 || ncb * T.nrt * 4 <= 512)) ? 2 : 1;
-  if (ks == 2) ncb = ceil_div(T.ntiles, 4);
-  T.nrg = ceil_div(T.nrt, rm);
-  T.nwork = ncb * T.nrg;
+  const GemmPlan P = plan_prior_gemm(T.ntiles, T.nslices, T.nrt, T.epi, g_gemm_rm, g_gemm_ks);
+  T.nrg = ceil_div(T.nrt, P.rm);
+  T.nwork = P.ncb * T.nrg;
   T.per_xcd = ceil_div(T.nwork, 8);
   const dim3 grid(T.per_xcd * 8), block(256);
   const size_t lds = 4 * GEMM_LDS_WAVE * sizeof(float);
-  if (rm == 2) HA_LAUNCH(prior_gemm_kernel<2>, grid, block, lds, st, T);
-  else if (ks == 2) HA_LAUNCH((prior_gemm_kernel<1, 2>), grid, block, lds, st, T);
-  else HA_LAUNCH(prior_gemm_kernel<1>, grid, block, lds, st, T);
+  const int shape = P.rm * 100 + P.ks * 10 + P.tn;
+  switch (shape) {
+    case 212: HA_LAUNCH(prior_gemm_kernel<2>, grid, block, lds, st, T); break;
+    case 112: HA_LAUNCH(prior_gemm_kernel<1>, grid, block, lds, st, T); break;
+    case 122: HA_LAUNCH((prior_gemm_kernel<1, 2>), grid, block, lds, st, T); break;
+    case 142: HA_LAUNCH((prior_gemm_kernel<1, 4>), grid, block, lds, st, T); break;
+    case 111: HA_LAUNCH((prior_gemm_kernel<1, 1, 1>), grid, block, lds, st, T); break;
+    case 121: HA_LAUNCH((prior_gemm_kernel<1, 2, 1>), grid, block, lds, st, T); break;
+    case 141: HA_LAUNCH((prior_gemm_kernel<1, 4, 1>), grid, block, lds, st, T); break;
+    default: HA_REQUIRE(false, "prior GEMM: no kernel for RM %d KS %d TN %d", P.rm, P.ks, P.tn);
+  }
   HA_LAUNCH_CHECK();
   return HA_OK;
 }
