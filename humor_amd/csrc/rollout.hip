@@ -14,6 +14,7 @@
 // 64-channel K-slice (one or two GroupNorm groups: statistics are lane-local, plus one cross-half shuffle for 64-channel
 // groups); NW waves of a block split K further and reduce through LDS; blocks split K across the chip and the consumer
 // layer's prologue sums those partial slabs (the launch-boundary reduce).
+#include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
@@ -41,6 +42,7 @@ constexpr int MAXL = 8;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float vf4 __attribute__((ext_vector_type(4)));
+typedef float vf2 __attribute__((ext_vector_type(2)));
 
 // offset of channel c inside one row's view of a quad-interleaved tile: element (c, row) of tile rt of a C-channel slab
 // (C % 4 == 0) is slab[rt * C * 32 + row * 4 + qoff(c)]
@@ -54,6 +56,10 @@ int g_gemm_rm = 0;    // row tiles per wave of the batched prior GEMM (ha_tune_s
 // GroupNorm take one column tile per wave (plan_prior_gemm: a frame-0 VPoser decode is 16 waves in the plain form, the launch lasts exactly
 // one wave's serial chain).  0 = off (plain form everywhere), 3 = force the deepest split also for large GEMMs (measured slower).
 int g_gemm_ks = 2;
+// ha_tune_set "gemm_fold" (default 1): layout-only passes around the batched GEMMs are folded into the neighbouring GEMM's epilogue (row-major
+// store: prior_mu / prior_var of the roll-out, y and g_x of ha_mlp_*) or into its first K slice (row-major A operand: x of ha_mlp_forward
+// up to 64 wide); 0 = the separate prior_io / mlp_out / transpose_in launches (A/B runs, tests).
+int g_gemm_fold = 1;
 // ha_tune_set "rollout_groups": 0 = auto, n >= 1 = split the batch into (at most) n row groups that run the chain side by side on
 // their own HIP streams (fork / join on the caller's stream with events; capturable), each with its own stash region and its steps
 // issued round-robin.  Sequences are independent, but side-by-side chains only pay where they change the launch policy: dispatch is
@@ -490,6 +496,7 @@ struct GemmTask {
   const float* Wp; const float* bias;     // packed weights [ntiles][nslices][8][64][4]; bias or null
   int ntiles, nslices, Nout;              // 32-column output tiles, 64-channel K slices, valid output columns
   const float* src; int Csrc;             // A operand: finished slab [row tiles][Csrc][32]
+  int src_rows;                           // > 0: the A operand is a ROW-MAJOR array [src_rows][Csrc] instead (Csrc <= 64, one K slice: no layout pass in front)
   int nrt;                                // row tiles
   int epi;                                // 0 raw -> dst_h | 1 raw -> dst_h, ReLU(GroupNorm(.)) -> dst_a | 3 GroupNorm-ReLU adjoint (with hsrc) -> dst_a
                                           // 4 LeakyReLU(raw) -> dst_a | 5 LeakyReLU adjoint (hsrc = the forward's activation) -> dst_a
@@ -498,6 +505,13 @@ struct GemmTask {
   const float* hsrc; int Ch;              // epi 3: forward pre-activations of the same channels [row tiles][Ch][32]
   float* dst_h; float* dst_a; int Cdst;   // output slabs [row tiles][Cdst][32]
   int nrg, nwork, per_xcd;                // row groups of RM tiles, work items = column blocks x row groups, items per XCD
+  // epi 0, optional: the finished tile also goes straight to a row-major destination (no layout pass behind the launch).  Row tile
+  // i = t * rm_RT + rtl, row rr of it is row r = rtl * 32 + rr of step t and lands at line r * rm_S + t of rm_w floats; rows
+  // r >= rm_rows and columns >= rm_C are not written.  Columns [0, rm_split) -> rm_dst, columns [rm_split, rm_C) -> expf(.) to rm_dst2
+  // (the prior's mean | log-variance; a plain output has rm_split = rm_C = rm_w).  rm_vec2: every line and both column ranges start
+  // 8-byte aligned (126- and 96-wide lines are no more than that), so the lane stores float pairs; otherwise single floats.
+  float* rm_dst; float* rm_dst2;
+  int rm_RT, rm_S, rm_rows, rm_w, rm_C, rm_split, rm_vec2;
 };
 
 constexpr int GEMM_LDS_WAVE = 2 * 8 * 132;    // floats of epilogue staging per wave: [column tile][quad][32 rows x 4 + pad]
@@ -524,6 +538,55 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
 #pragma unroll
   for (int m = 0; m < RM; ++m) rt[m] = rg * RM + m < T.nrt ? rg * RM + m : T.nrt - 1;
 
+  // the epilogue's view: (row, 32 channels of one column tile) per lane.  None of its operands' addresses depends on the accumulators: the
+  // loaders below are called as ONE batch as soon as the accumulators are staged (their registers are free by then), in flight under the
+  // LDS exchange.  Fetched where each is used they were two to three dependent, fully exposed memory round trips of a wave that has its
+  // SIMD to itself (square prior products 42.9 -> 39.0 us); fetched BEFORE the K loop they gain nothing over the batch, cost the small
+  // launches 0.5-1 us each and every form its second wave per SIMD (profiles/r08_gemm_epilogue).
+  const int row = lane & 31, hh = lane >> 5;
+  const int ct = hh ? ct0 + 1 : ct0;                  // this lane's column tile (TN = 1: the upper half-wave has none)
+  const bool ct_ok = hh < TN && ct < T.ntiles;
+  const int hs = hh < TN ? hh : 0;                    // staged tile this lane reads
+  float gam[32], bet[32], bia[32], hpre[RM][32];
+  auto load_affine = [&]() {
+    if ((T.epi == 1 || T.epi == 3) && ct_ok) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const vf4 g4 = *reinterpret_cast<const vf4*>(T.gamma + ct * 32 + 4 * j);
+        const vf4 b4 = *reinterpret_cast<const vf4*>(T.beta + ct * 32 + 4 * j);
+        gam[4 * j] = g4.x; gam[4 * j + 1] = g4.y; gam[4 * j + 2] = g4.z; gam[4 * j + 3] = g4.w;
+        bet[4 * j] = b4.x; bet[4 * j + 1] = b4.y; bet[4 * j + 2] = b4.z; bet[4 * j + 3] = b4.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 32; ++k) { gam[k] = 1.f; bet[k] = 0.f; }
+    }
+  };
+  auto load_bias = [&]() {      // (only read where T.bias && ct_ok; the packed bias is zero-padded to whole 32-column tiles)
+    if (T.bias && ct_ok) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const vf4 b4 = *reinterpret_cast<const vf4*>(T.bias + ct * 32 + 4 * j);
+        bia[4 * j] = b4.x; bia[4 * j + 1] = b4.y; bia[4 * j + 2] = b4.z; bia[4 * j + 3] = b4.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 32; ++k) bia[k] = 0.f;
+    }
+  };
+  auto load_h = [&](int m) {    // epi 3 / 5: the forward's values of this lane's channels (a lane without a tile reads tile ct0, or 0 beyond the last)
+    if (T.epi == 3 || T.epi == 5) {
+      const float* hp = T.hsrc + (size_t)rt[m] * T.Ch * 32 + (size_t)((ct_ok ? ct : (tile_ok ? ct0 : 0)) * 8) * 128 + (size_t)row * 4;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const vf4 q = *reinterpret_cast<const vf4*>(hp + (size_t)j * 128);
+        hpre[m][4 * j] = q.x; hpre[m][4 * j + 1] = q.y; hpre[m][4 * j + 2] = q.z; hpre[m][4 * j + 3] = q.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 32; ++k) hpre[m][k] = 0.f;
+    }
+  };
   f32x16 acc[RM][TN];
 #pragma unroll
   for (int m = 0; m < RM; ++m)
@@ -560,7 +623,8 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
         if (TN == 2) acc[m][TN - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][kp], b1[kp], acc[m][TN - 1], 0, 0, 0);
       }
   };
-  const int nfull_all = T.Csrc / SLICE < T.nslices ? T.Csrc / SLICE : T.nslices;      // slices whose 64 channels all exist in the slab
+  // slices whose 64 channels all exist in the slab (a row-major operand takes the guarded loader of the ragged tail)
+  const int nfull_all = T.src_rows > 0 ? 0 : (T.Csrc / SLICE < T.nslices ? T.Csrc / SLICE : T.nslices);
   // this wave's share of the full slices: [sbeg, nfull)
   const int per_part = (nfull_all + KS - 1) / KS;
   const int sbeg = KS == 1 ? 0 : (kpart * per_part < nfull_all ? kpart * per_part : nfull_all);
@@ -592,30 +656,30 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
     // ragged K tail (339 = 5 x 64 + 19 state channels, 96 = 64 + 32 prior outputs): quads beyond the slab width read as zero
     float a[RM][32], b0[32], b1[32];
     load_b(nfull_all, b0, b1);
+    if (T.src_rows > 0) {
+      // lane (row, hi) holds channels 32 hi + kp of row rt * 32 + row, zero beyond the array as the slab's padding is (all loads unconditional)
+      // (32 single-float loads per lane, lanes a whole line apart: meant for the narrow first layer of a small batch, where the launch sits at
+      // the floor of a short kernel anyway -- not tuned for many rows)
 #pragma unroll
-    for (int m = 0; m < RM; ++m) load_frag_n<true>(T.src, 1, 0, T.Csrc, rt[m], nfull_all * SLICE, lane, a[m]);
+      for (int m = 0; m < RM; ++m) {
+        const int r = rt[m] * 32 + (lane & 31);
+#pragma unroll
+        for (int kp = 0; kp < 32; ++kp) {
+          const int c = 32 * (lane >> 5) + kp;
+          const bool ok = r < T.src_rows && c < T.Csrc;
+          const float x = T.src[ok ? (size_t)r * T.Csrc + c : 0];
+          a[m][kp] = ok ? x : 0.f;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int m = 0; m < RM; ++m) load_frag_n<true>(T.src, 1, 0, T.Csrc, rt[m], nfull_all * SLICE, lane, a[m]);
+    }
     mma(a, b0, b1);
   }
 
   // ---- epilogue: accumulators -> (row, 32 channels of one column tile) per lane through the wave's LDS slice -----------------
   float* sl = smem + wave * GEMM_LDS_WAVE;
-  const int row = lane & 31, hh = lane >> 5;
-  const int ct = hh ? ct0 + 1 : ct0;                  // this lane's column tile (TN = 1: the upper half-wave has none)
-  const bool ct_ok = hh < TN && ct < T.ntiles;
-  const int hs = hh < TN ? hh : 0;                    // staged tile this lane reads
-  float gam[32], bet[32];
-  if ((T.epi == 1 || T.epi == 3) && ct_ok) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const vf4 g4 = *reinterpret_cast<const vf4*>(T.gamma + ct * 32 + 4 * j);
-      const vf4 b4 = *reinterpret_cast<const vf4*>(T.beta + ct * 32 + 4 * j);
-      gam[4 * j] = g4.x; gam[4 * j + 1] = g4.y; gam[4 * j + 2] = g4.z; gam[4 * j + 3] = g4.w;
-      bet[4 * j] = b4.x; bet[4 * j + 1] = b4.y; bet[4 * j + 2] = b4.z; bet[4 * j + 3] = b4.w;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 32; ++k) { gam[k] = 1.f; bet[k] = 0.f; }
-  }
 #pragma unroll
   for (int m = 0; m < RM; ++m) {
     // accumulator register i of lane l: row (i&3) + 8 (i>>2) + 4 (l>>5), column l&31
@@ -626,6 +690,13 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
         const int r = (i & 3) + 8 * (i >> 2) + 4 * hh, col = lane & 31;
         sl[(c * 8 + (col >> 2)) * 132 + r * 4 + (col & 3)] = acc[m][c][i];
       }
+    if (m == 0 && kpart == 0) {      // (only the wave that finishes the tile; in flight under the LDS exchange, not sunk to their uses)
+      load_affine();
+      load_bias();
+#pragma unroll
+      for (int mm = 0; mm < RM; ++mm) load_h(mm);
+      HA_SCHED_FENCE();
+    }
     if (KS == 1) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -650,31 +721,56 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     const bool live = ct_ok && rg * RM + m < T.nrt;
-    if (T.bias && ct_ok) {       // the packed bias is zero-padded to whole 32-column tiles
+    if (T.bias && ct_ok) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const vf4 b4 = *reinterpret_cast<const vf4*>(T.bias + ct * 32 + 4 * j);
-        v[4 * j] += b4.x; v[4 * j + 1] += b4.y; v[4 * j + 2] += b4.z; v[4 * j + 3] += b4.w;
-      }
+      for (int k = 0; k < 32; ++k) v[k] += bia[k];
     }
     const size_t o = (size_t)rt[m] * T.Cdst * 32 + (size_t)(ct * 8) * 128 + (size_t)row * 4;
     auto store32 = [&](float* base, const float (&x)[32]) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) *reinterpret_cast<vf4*>(base + o + (size_t)j * 128) = vf4{x[4 * j], x[4 * j + 1], x[4 * j + 2], x[4 * j + 3]};
     };
-    if (T.epi <= 1 && live) store32(T.dst_h, v);
+    if (T.epi <= 1 && live && T.dst_h) store32(T.dst_h, v);
+    if (T.rm_dst && live) {
+      const int tile = rg * RM + m, t = tile / T.rm_RT, r = (tile - t * T.rm_RT) * 32 + row;
+      if (r < T.rm_rows) {
+        const size_t line = ((size_t)r * T.rm_S + t) * T.rm_w;
+        float* const d0 = T.rm_dst + line;
+        float* const d1 = T.rm_dst2 ? T.rm_dst2 + line - T.rm_split : d0;
+        float x[32];
+        // (the mean passes through `+ 0.f` as it did through the layout pass's slab sum; the log-variance through the same expf)
+        if (T.rm_dst2) {
+#pragma unroll
+          for (int k = 0; k < 32; ++k) {
+            const float e = expf(v[k]), p = v[k] + 0.f;      // (both sides computed: a select, not 32 divergent branches)
+            x[k] = ct * 32 + k >= T.rm_split ? e : p;
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < 32; ++k) x[k] = v[k];
+        }
+        if (T.rm_vec2) {      // (the split is even: a pair never straddles it)
+#pragma unroll
+          for (int k = 0; k < 32; k += 2) {
+            const int c = ct * 32 + k;
+            if (c < T.rm_C) *reinterpret_cast<vf2*>((c >= T.rm_split ? d1 : d0) + c) = vf2{x[k], x[k + 1]};
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < 32; ++k) {
+            const int c = ct * 32 + k;
+            if (c < T.rm_C) (c >= T.rm_split ? d1 : d0)[c] = x[k];
+          }
+        }
+      }
+    }
     if (T.epi == 4) {
 #pragma unroll
       for (int k = 0; k < 32; ++k) v[k] = v[k] > 0.f ? v[k] : v[k] * T.slope;
       if (live) store32(T.dst_a, v);
     } else if (T.epi == 5) {       // sign(LeakyReLU(h)) = sign(h): the stored activation stands in for the pre-activation
-      const float* hp = T.hsrc + (size_t)rt[m] * T.Ch * 32 + (size_t)((ct_ok ? ct : ct0) * 8) * 128 + (size_t)row * 4;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const vf4 q = *reinterpret_cast<const vf4*>(hp + (size_t)j * 128);
-        v[4 * j] *= q.x > 0.f ? 1.f : T.slope; v[4 * j + 1] *= q.y > 0.f ? 1.f : T.slope;
-        v[4 * j + 2] *= q.z > 0.f ? 1.f : T.slope; v[4 * j + 3] *= q.w > 0.f ? 1.f : T.slope;
-      }
+      for (int k = 0; k < 32; ++k) v[k] *= hpre[m][k] > 0.f ? 1.f : T.slope;
       if (live) store32(T.dst_a, v);
     } else if (T.epi == 1) {
       const float inv_n = 1.0f / (float)T.group;
@@ -682,16 +778,9 @@ __global__ __launch_bounds__(256) void prior_gemm_kernel(GemmTask T) {
       else gn_apply<2>(1, gam, bet, inv_n, v, v);
       if (live) store32(T.dst_a, v);
     } else if (T.epi == 3) {
-      float h[32];
-      const float* hp = T.hsrc + (size_t)rt[m] * T.Ch * 32 + (size_t)((ct_ok ? ct : ct0) * 8) * 128 + (size_t)row * 4;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const vf4 q = *reinterpret_cast<const vf4*>(hp + (size_t)j * 128);
-        h[4 * j] = q.x; h[4 * j + 1] = q.y; h[4 * j + 2] = q.z; h[4 * j + 3] = q.w;
-      }
       const float inv_n = 1.0f / (float)T.group;
-      if (T.group == SLICE) gn_apply<1>(3, gam, bet, inv_n, h, v);
-      else gn_apply<2>(3, gam, bet, inv_n, h, v);
+      if (T.group == SLICE) gn_apply<1>(3, gam, bet, inv_n, hpre[m], v);
+      else gn_apply<2>(3, gam, bet, inv_n, hpre[m], v);
       if (live) store32(T.dst_a, v);
     }
   }
@@ -1791,6 +1880,12 @@ static GemmPlan plan_prior_gemm(int ntiles, int nslices, int nrt, int epi, int r
 // one batched prior layer (forward l >= 0 / adjoint) over nrt = S * RT row tiles
 static int launch_prior_gemm(GemmTask& T, hipStream_t st) {
   HA_REQUIRE((T.epi != 1 && T.epi != 3) || (T.ntiles % 2 == 0 && (T.group == 32 || T.group == 64)), "prior GEMM: GroupNorm epilogue needs whole 64-column pairs");
+  HA_REQUIRE(!T.rm_dst || (T.epi == 0 && T.rm_RT >= 1 && T.rm_C <= T.ntiles * 32 && (T.rm_dst2 || T.rm_split >= T.rm_C)), "prior GEMM: bad row-major destination");
+  HA_REQUIRE(T.src_rows == 0 || (T.nslices == 1 && T.Csrc <= SLICE && T.src_rows <= T.nrt * 32), "prior GEMM: a row-major A operand is one K slice");
+  if (T.rm_dst) {
+    auto odd = [](const void* q) { return ((uintptr_t)q & 7) != 0; };
+    T.rm_vec2 = !(((T.rm_w | T.rm_C | T.rm_split) & 1) || odd(T.rm_dst) || (T.rm_dst2 && odd(T.rm_dst2)));
+  }
   const GemmPlan P = plan_prior_gemm(T.ntiles, T.nslices, T.nrt, T.epi, g_gemm_rm, g_gemm_ks);
   T.nrg = ceil_div(T.nrt, P.rm);
   T.nwork = P.ncb * T.nrg;
@@ -1813,7 +1908,9 @@ static int launch_prior_gemm(GemmTask& T, hipStream_t st) {
 }
 
 // forward of the whole prior network for all S steps (inputs: the state slabs x_0 .. x_{S-1})
-static int prior_forward_batched(const ha_humor_net* net, const StashLayout& L, float* stash, int S, hipStream_t st) {
+// prior_mu / prior_var [B][S][48] (null: the caller runs prior_io_kernel behind the last layer instead)
+static int prior_forward_batched(const ha_humor_net* net, const StashLayout& L, float* stash, int B, int S, float* prior_mu, float* prior_var,
+                                 hipStream_t st) {
   const int np = net->n_pri;
   for (int l = 0; l < np; ++l) {
     const PackedLayer& P = net->pri[l];
@@ -1829,6 +1926,10 @@ static int prior_forward_batched(const ha_humor_net* net, const StashLayout& L, 
       const PackedLayer& N = net->pri[l + 1];       // the GroupNorm between l and l+1 is stored with its consumer
       T.epi = 1; T.gamma = N.gamma; T.beta = N.beta; T.group = N.group;
       T.dst_a = stash + L.pri_act[l & 1];
+    } else if (prior_mu) {
+      // mean | exp(log-variance) leave the last layer's epilogue row-major; dst_h is still written (the adjoint's prior_io reads it)
+      T.rm_dst = prior_mu; T.rm_dst2 = prior_var;
+      T.rm_RT = L.RT; T.rm_S = S; T.rm_rows = B; T.rm_w = ZD; T.rm_split = ZD; T.rm_C = 2 * ZD;
     }
     int rc = launch_prior_gemm(T, st);
     if (rc != HA_OK) return rc;
@@ -2114,8 +2215,10 @@ static int rollout_forward_impl(const ha_humor_net* net, const CallPlan& plan, c
     return chain_decoder_step(net, L, B, S, t, stash, world, L.hsum, g, st);
   }
   if (prior_mu) {
-    int rc = prior_forward_batched(net, L, stash, S, st);
+    const bool fold = g_gemm_fold != 0 && net->pri[np - 1].Nout == 2 * ZD;
+    int rc = prior_forward_batched(net, L, stash, B, S, fold ? prior_mu : nullptr, fold ? prior_var : nullptr, st);
     if (rc != HA_OK) return rc;
+    if (fold) return HA_OK;
     PriorIOParams q;
     memset(&q, 0, sizeof(q));
     q.B = B; q.S = S; q.RT = RT;
@@ -2637,9 +2740,14 @@ extern "C" int ha_mlp_forward(const ha_mlp* m, int N, const float* x, int tail, 
   DeviceGuard guard(m->device);
   hipStream_t st = (hipStream_t)stream;
   const MlpLayout W = mlp_layout(m, N);
-  HA_LAUNCH(transpose_in_kernel, dim3(ceil_div((int)((size_t)W.nrt * m->in_pad * 32), 256)), dim3(256), 0, st, x, ws + W.xT, N, 1, m->in_dim,
-                     m->in_pad, W.nrt);
-  HA_LAUNCH_CHECK();
+  const int C = m->out_dim, Cpad = m->L[m->n - 1].Nout_pad;
+  const bool fold_y = g_gemm_fold != 0 && tail == HA_MLP_TAIL_NONE;      // (the 6-D tail stays a kernel: its groups of six straddle the 32-column tiles)
+  const bool fold_x = g_gemm_fold != 0 && m->in_dim <= SLICE;      // the first layer's whole K is one slice: it reads x row-major itself
+  if (!fold_x) {
+    HA_LAUNCH(transpose_in_kernel, dim3(ceil_div((int)((size_t)W.nrt * m->in_pad * 32), 256)), dim3(256), 0, st, x, ws + W.xT, N, 1, m->in_dim,
+                       m->in_pad, W.nrt);
+    HA_LAUNCH_CHECK();
+  }
   for (int l = 0; l < m->n; ++l) {
     const PackedLayer& P = m->L[l];
     const bool last = l + 1 == m->n;
@@ -2662,10 +2770,15 @@ extern "C" int ha_mlp_forward(const ha_mlp* m, int N, const float* x, int tail, 
         T.dst_h = ws + W.keep[l]; T.dst_a = ws + W.pp[l & 1];
       }
     }
+    if (l == 0 && fold_x) { T.src = x; T.Csrc = m->in_dim; T.src_rows = N; }
+    if (last && fold_y) {      // (no slab: without a tail nothing reads ws + W.out afterwards, mlp_gout_kernel takes it only for the 6-D tail)
+      T.dst_h = nullptr;
+      T.rm_dst = y; T.rm_RT = W.nrt; T.rm_S = 1; T.rm_rows = N; T.rm_w = T.rm_C = T.rm_split = C;
+    }
     int rc = launch_prior_gemm(T, st);
     if (rc != HA_OK) return rc;
   }
-  const int C = m->out_dim, Cpad = m->L[m->n - 1].Nout_pad;
+  if (fold_y) return HA_OK;
   const size_t items = tail == HA_MLP_TAIL_NONE ? (size_t)N * C : (size_t)N * (C / 6);
   HA_LAUNCH(mlp_out_kernel, dim3((unsigned)ceil_div((int)items, 256)), dim3(256), 0, st, ws + W.out, y, N, C, Cpad, tail);
   HA_LAUNCH_CHECK();
@@ -2692,8 +2805,11 @@ extern "C" int ha_mlp_backward(const ha_mlp* m, int N, const float* g_y, int tai
     T.ntiles = P.ntiles_b; T.nslices = P.nslices_b; T.Nout = P.Cin;
     T.src = ws + W.pp[l & 1]; T.Csrc = P.Nout_pad;
     T.nrt = W.nrt; T.Cdst = P.Nin_pad;
-    if (l == 0) { T.epi = 0; T.dst_h = ws + W.gx; }
-    else {
+    if (l == 0) {
+      T.epi = 0;
+      if (g_gemm_fold != 0) { T.rm_dst = g_x; T.rm_RT = W.nrt; T.rm_S = 1; T.rm_rows = N; T.rm_w = T.rm_C = T.rm_split = m->in_dim; }
+      else T.dst_h = ws + W.gx;
+    } else {
       T.hsrc = ws + W.keep[l - 1]; T.Ch = m->L[l - 1].Nout_pad;
       T.dst_a = ws + W.pp[(l - 1) & 1];
       if (m->act == HA_MLP_LEAKY_RELU) { T.epi = 5; T.slope = m->slope; }
@@ -2702,6 +2818,7 @@ extern "C" int ha_mlp_backward(const ha_mlp* m, int N, const float* g_y, int tai
     int rc = launch_prior_gemm(T, st);
     if (rc != HA_OK) return rc;
   }
+  if (g_gemm_fold != 0) return HA_OK;
   HA_LAUNCH(mlp_out_kernel, dim3((unsigned)ceil_div((int)((size_t)N * m->in_dim), 256)), dim3(256), 0, st, ws + W.gx, g_x, N, m->in_dim,
                      m->L[0].Nin_pad, 0);
   HA_LAUNCH_CHECK();

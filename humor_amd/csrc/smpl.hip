@@ -46,7 +46,7 @@ int g_skin_variant = -1;
 int g_dense_gA_sparse = 2;   // ha_tune_set("dense_gA_sparse"): dL/dA of the dense backward -- 2 (default) = MFMA product over the joints each 64-vertex
                              // chunk touches (205 us at N = 1920), 1 = by joint lists (255 us), 0 = dense 64-column MFMA product (417 us)
 int g_dense_bwd_waves = 0;   // ha_tune_set("dense_bwd_waves"): wave-count target of the dense backward's K split (0 = default)
-extern int g_layer_finish, g_gemm_rm, g_rollout_groups, g_gemm_ks, g_rollout_persist, g_rollout_persist_bwd, g_rollout_persist_inject, g_rollout_pipe, g_rollout_pipe_bwd;   // rollout.hip
+extern int g_layer_finish, g_gemm_rm, g_rollout_groups, g_gemm_ks, g_gemm_fold, g_rollout_persist, g_rollout_persist_bwd, g_rollout_persist_inject, g_rollout_pipe, g_rollout_pipe_bwd;   // rollout.hip
 extern unsigned g_cu_poison;   // debug.hip
 }
 extern "C" int ha_tune_set(const char* key, int value) {
@@ -58,6 +58,7 @@ extern "C" int ha_tune_set(const char* key, int value) {
   if (strcmp(key, "gemm_rm") == 0) { ha::g_gemm_rm = value; return HA_OK; }
   if (strcmp(key, "rollout_groups") == 0) { ha::g_rollout_groups = value; return HA_OK; }
   if (strcmp(key, "gemm_ks") == 0) { ha::g_gemm_ks = value; return HA_OK; }
+  if (strcmp(key, "gemm_fold") == 0) { ha::g_gemm_fold = value; return HA_OK; }
   if (strcmp(key, "rollout_persist") == 0) { ha::g_rollout_persist = value; return HA_OK; }
   if (strcmp(key, "rollout_persist_bwd") == 0) { ha::g_rollout_persist_bwd = value; return HA_OK; }
   if (strcmp(key, "rollout_pipe") == 0) { ha::g_rollout_pipe = value; return HA_OK; }

@@ -34,7 +34,7 @@ const char* ha_last_error(void);
 int ha_abi_version(void);
 /* Writes the device's gcnArchName (e.g. "gfx950:sramecc+:xnack-") into buf. */
 int ha_device_arch(int device, char* buf, int buflen);
-/* Development knobs for kernel launch variants (A/B measurements), process-wide: "skin_variant" (-1 = auto), "layer_finish" (0 never / 1 auto / 2 always use the GroupNorm finishing pass), "gemm_rm" (row tiles per wave of the batched prior GEMM: 0 by size / 1 / 2), "rollout_persist" / "rollout_persist_bwd" (0 = launch chain; 1 = persistent kernels, 3 = with write-through publishes), "rollout_pipe" / "rollout_pipe_bwd" (batches of more than 32 sequences: 1 = the layer-parallel pipelined persistent kernels, 0 = launch chain; set the adjoint knobs before the forward call), "rollout_persist_inject" (test hook: 1 = the next persistent forwards drop one CU of team 0, so that the failure path -- NaN results, error word -- can be exercised), "cu_poison" (test hook: != 0 = every kernel launch of this library is preceded by a kernel that fills the LDS and the vector registers of every CU with a bit pattern -- 1 = a quiet NaN, else the value itself -- so that a read of state the kernel did not write shows on every box). */
+/* Development knobs for kernel launch variants (A/B measurements), process-wide: "skin_variant" (-1 = auto), "layer_finish" (0 never / 1 auto / 2 always use the GroupNorm finishing pass), "gemm_rm" (row tiles per wave of the batched prior GEMM: 0 by size / 1 / 2), "gemm_ks" (short-chain forms of the small batched GEMMs: 0 = plain form everywhere, 2 = by the launch policy, 3 = force the deepest K split), "gemm_fold" (1 = the layout-only passes around the batched GEMMs -- prior_mu / prior_var of a roll-out, y / g_x / a narrow x of ha_mlp_* -- are done by the GEMM itself, 0 = separate launches), "rollout_persist" / "rollout_persist_bwd" (0 = launch chain; 1 = persistent kernels, 3 = with write-through publishes), "rollout_pipe" / "rollout_pipe_bwd" (batches of more than 32 sequences: 1 = the layer-parallel pipelined persistent kernels, 0 = launch chain; set the adjoint knobs before the forward call), "rollout_persist_inject" (test hook: 1 = the next persistent forwards drop one CU of team 0, so that the failure path -- NaN results, error word -- can be exercised), "cu_poison" (test hook: != 0 = every kernel launch of this library is preceded by a kernel that fills the LDS and the vector registers of every CU with a bit pattern -- 1 = a quiet NaN, else the value itself -- so that a read of state the kernel did not write shows on every box). */
 int ha_tune_set(const char* key, int value);
 /* Test support: fills the LDS and every VGPR / AGPR of all CUs with `pattern` (0 = quiet NaN) on `stream`; with `surviving_words` non-null it then
  * synchronises the stream and counts the LDS words (of 256 x 40960) a following kernel still finds holding the pattern -- 0 means this box clears
