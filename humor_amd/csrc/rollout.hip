@@ -2110,6 +2110,15 @@ extern "C" int ha_debug_persist_layout(const ha_humor_net* net, int B, int S, in
 }
 #endif
 
+// read-only query for the tests (not in include/humor_amd.h): the form launch_prior_gemm gives a launch of this size behind epilogue `epi`
+// under the live gemm_rm / gemm_ks knobs -- out4 = {RM, KS, TN, column blocks}
+extern "C" int ha_debug_gemm_plan(int ntiles, int nslices, int nrt, int epi, int* out4) {
+  HA_REQUIRE(out4 && ntiles >= 1 && nslices >= 1 && nrt >= 1 && epi >= 0 && epi <= 5 && epi != 2, "ha_debug_gemm_plan: bad argument");
+  const GemmPlan P = plan_prior_gemm(ntiles, nslices, nrt, epi, g_gemm_rm, g_gemm_ks);
+  out4[0] = P.rm; out4[1] = P.ks; out4[2] = P.tn; out4[3] = P.ncb;
+  return HA_OK;
+}
+
 #ifdef HA_LAYER_TIMING
 extern "C" int ha_debug_layer_timing(unsigned long long* out /* [64][10] */, unsigned int* launches) {
   HA_CHECK_HIP(hipDeviceSynchronize());

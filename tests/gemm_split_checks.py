@@ -79,6 +79,8 @@ def check_net(lib, device, dims, act, N, seed=0, verbose=True):
     y2, gx2 = run(lib, device, f, x, w, 2)
     y2b, gx2b = run(lib, device, f, x, w, 2)
     nrt = -(-N // 32)
+    import gemm_forms_checks as GF      # (imports this module)
+    GF.assert_launch_unsplit_agrees(lib, dims, act, N)      # the Python restatement below against plan_prior_gemm itself
     fwd_same = all(launch_unsplit(dims[i], dims[i + 1], nrt) for i in range(len(dims) - 1))
     bwd_same = fwd_same and all(launch_unsplit(dims[i + 1], dims[i], nrt) for i in range(len(dims) - 1))      # (the adjoint reads the forward's stash)
     err = lambda a, r: (a.double() - r).abs().max().item()
