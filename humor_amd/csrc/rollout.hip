@@ -818,6 +818,13 @@ struct GlueParams {
   float* g_past0;           // [B][D_IN] (final collect only)
 };
 
+// SMPL-joint feedback (glue_fwd_fb_kernel only): the next input's joints come from forward kinematics over the prediction
+struct GlueFeedback {
+  const float* rest;        // [B][22][3] rest joints J(beta) of every sequence; null: no feedback
+  int nrounds;              // pointer-jumping rounds: 2^nrounds > depth of the 22-joint tree
+  int anc[NJT];             // joint j: its 2^r-th ancestor in bits [5r, 5r+5), 31 = none
+};
+
 __device__ __forceinline__ float tsum(const float* base, int nsplit, int RT, int C, int rt, int c, int row) {
   return base ? slab_sum(base, nsplit, RT, C, rt, c, row) : 0.f;
 }
@@ -936,139 +943,24 @@ __device__ __forceinline__ void predict_root(const float* sX, const float* sRAW,
 
 // Forward glue of step t.  Three waves per sequence (the same split as glue_bwd_kernel): wave 0 the root (lane 0), wave 1
 // the joints, wave 2 the body rotations, contact logits and the prior outputs.
+//
+// FB (humor_model.py:894-954, model_use_smpl_joint_inputs): the joints of the NEXT input are not the regressed ones but those of the
+// SMPL+H body model posed with this step's own prediction -- its first 22 joints are forward kinematics over the 22 predicted
+// rotations (each through the reference's matrix -> axis-angle -> matrix round trip) and the sequence's rest joints.  Waves 0 and 2
+// leave their rotations in LDS, the joint wave runs the chain by pointer jumping (as smpl_frame_fwd_kernel does) with lane = joint.
+// The world outputs keep the regressed joints, the joint velocities are not replaced.
 template <int ROTW, bool DELTA>
 __global__ __launch_bounds__(192) void glue_fwd_kernel(GlueParams p) {
-  using RL = RawLayout<ROTW>;
-  const int r = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int rt = r >> 5, rr = r & 31;
-  const bool valid = r < p.B;
-  float* XN = p.xT_next + (size_t)rt * D_INP * 32 + (size_t)rr * 4;
-  if (!valid) {
-    for (int c = tid; c < D_INP; c += 192) XN[qoff(c)] = 0.f;
-    return;
-  }
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sX = smem + S_X;
-  float* sRAW = smem + S_RAW;
-  float* sSH = smem + S_SH;
-  stage_slabs<1, 192>(sX, p.xT, 1, p.RT, D_INP, D_IN, rt, rr, tid, false);
-  stage_slabs<1, 192>(sRAW, p.dec_out, p.dec_nsplit, p.RT, p.dec_pad, RL::D, rt, rr, tid, false);
-  if (tid == 0) XN[qoff(D_IN)] = 0.f;      // pad channel of the next state slab
-  float G[9], gt[3], t2j[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) G[i] = 0.f;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { gt[c] = 0.f; t2j[c] = 0.f; }
-  if (wave < 2) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) G[i] = p.Gs[(size_t)r * 12 + i];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { gt[c] = p.Gs[(size_t)r * 12 + 9 + c]; t2j[c] = p.t2j[(size_t)r * 3 + c]; }
-  }
-  __syncthreads();
-  float* WO = p.world + ((size_t)r * p.S + p.t) * D_STATE;
-  PredState s;
-  if (wave == 0) {
-    // heading alignment from the predicted root orientation
-    if (lane == 0) {
-      predict_root<ROTW, DELTA>(sX, sRAW, s);
-      W2A wa;
-      w2a_fwd(s.pR, wa);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) sSH[i] = wa.W[i];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) sSH[9 + c] = s.ptrans[c];
-    }
-  } else if (wave == 1) {
-    if (lane < NJT) predict_joints<ROTW, DELTA>(sX, sRAW, lane, s);
-  } else {
-    if (lane >= 1 && lane < NJT) {
-      predict_body<ROTW, DELTA>(sX, sRAW, lane - 1, s);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) {
-        XN[qoff(18 + 9 * (lane - 1) + i)] = s.pB[i];
-        WO[18 + 9 * (lane - 1) + i] = s.pB[i];
-      }
-    }
-    if (lane >= 32 && lane < 32 + 9) {
-      const int c = lane - 32;
-      WO[339 + c] = sRAW[RL::CONT + c];
-    }
-    if (p.prior_mu && lane < ZD) {
-      const float mu = slab_sum(p.pri_out, p.pri_nsplit, p.RT, p.pri_pad, rt, lane, rr);
-      const float lv = slab_sum(p.pri_out, p.pri_nsplit, p.RT, p.pri_pad, rt, ZD + lane, rr);
-      p.prior_mu[((size_t)r * p.S + p.t) * ZD + lane] = mu;
-      p.prior_var[((size_t)r * p.S + p.t) * ZD + lane] = expf(lv);
-    }
-  }
-  __syncthreads();
-  float W[9], ptr[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) W[i] = sSH[i];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) ptr[c] = sSH[9 + c];
-  const float wt[3] = {-ptr[0], -ptr[1], 0.f};
+  constexpr bool FB = false;
+  const GlueFeedback fb = {};
+#include "glue_fwd_body.inc"
+}
 
-  if (wave == 1 && lane < NJT) {
-    const int j = lane;
-    float q[3], o[3];
-    // next input: W (pj + wt + t2j) - t2j ; W jv
-#pragma unroll
-    for (int c = 0; c < 3; ++c) q[c] = s.pj[c] + wt[c] + t2j[c];
-    mat3_vec(W, q, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) XN[qoff(207 + 3 * j + c)] = o[c] - t2j[c];
-    mat3_vec(W, s.jv, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) XN[qoff(273 + 3 * j + c)] = o[c];
-    // world: G^T (pj + t2j) - t2j - gt ; G^T jv
-#pragma unroll
-    for (int c = 0; c < 3; ++c) q[c] = s.pj[c] + t2j[c];
-    mat3_tvec(G, q, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) WO[207 + 3 * j + c] = o[c] - t2j[c] - gt[c];
-    mat3_tvec(G, s.jv, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) WO[273 + 3 * j + c] = o[c];
-  }
-  if (wave == 0 && lane == 0) {
-    float q[3], o[3], M[9];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) q[c] = s.ptrans[c] + wt[c];
-    mat3_vec(W, q, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) XN[qoff(c)] = o[c];
-    mat3_vec(W, s.ptvel, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) XN[qoff(3 + c)] = o[c];
-    mat3_mul(W, s.pR, M);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) XN[qoff(6 + i)] = M[i];
-    mat3_vec(W, s.prvel, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) XN[qoff(15 + c)] = o[c];
-    // world
-    float wtr[3];
-    mat3_tvec(G, s.ptrans, wtr);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { wtr[c] -= gt[c]; WO[c] = wtr[c]; }
-    mat3_tvec(G, s.ptvel, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) WO[3 + c] = o[c];
-    mat3_tmul(G, s.pR, M);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) WO[6 + i] = M[i];
-    mat3_tvec(G, s.prvel, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) WO[15 + c] = o[c];
-    // accumulate the world transform
-    mat3_mul(G, W, M);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) p.Gs_next[(size_t)r * 12 + i] = M[i];
-    p.Gs_next[(size_t)r * 12 + 9] = -wtr[0];
-    p.Gs_next[(size_t)r * 12 + 10] = -wtr[1];
-    p.Gs_next[(size_t)r * 12 + 11] = 0.f;
-  }
+// the feedback variant exists for the released configuration only (out_rot_rep='aa', output_delta=True)
+__global__ __launch_bounds__(192) void glue_fwd_fb_kernel(GlueParams p, GlueFeedback fb) {
+  constexpr int ROTW = 3;
+  constexpr bool DELTA = true, FB = true;
+#include "glue_fwd_body.inc"
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -1404,8 +1296,12 @@ __global__ __launch_bounds__(256) void glue_bwd_kernel(GlueParams p) {
   }
 }
 
-static inline void launch_glue_fwd(int rotw, bool delta, int rows, hipStream_t st, const GlueParams& g) {
+static inline void launch_glue_fwd(int rotw, bool delta, int rows, hipStream_t st, const GlueParams& g, const GlueFeedback* fb = nullptr) {
   const size_t lds = S_TOTAL_BWD * sizeof(float);
+  if (fb) {      // (the entry point has checked rotw == 3 && delta)
+    HA_LAUNCH(glue_fwd_fb_kernel, dim3(rows), dim3(192), lds, st, g, *fb);
+    return;
+  }
 #define HA_GLUE_FWD(R, D) HA_LAUNCH((glue_fwd_kernel<R, D>), dim3(rows), dim3(192), lds, st, g)
   if (delta) { if (rotw == 3) HA_GLUE_FWD(3, true); else if (rotw == 6) HA_GLUE_FWD(6, true); else HA_GLUE_FWD(9, true); }
   else { if (rotw == 3) HA_GLUE_FWD(3, false); else if (rotw == 6) HA_GLUE_FWD(6, false); else HA_GLUE_FWD(9, false); }
@@ -2154,7 +2050,7 @@ enum { PH_BEGIN = 0, PH_STEP = 1, PH_END = 2 };
 // `g` arrives zeroed but for the caller's own glue fields (the sampling roll-out's prior outputs); `hsum`: the layer launches also write
 // the summed pre-activations back for the adjoint.
 static int chain_decoder_step(const ha_humor_net* net, const StashLayout& L, int B, int S, int t, float* stash, float* world, bool hsum,
-                              GlueParams& g, hipStream_t st) {
+                              GlueParams& g, hipStream_t st, const GlueFeedback* fb = nullptr) {
   const int RT = L.RT, nd = net->n_dec;
   float* sp = stash + L.steps + (size_t)t * L.per_step;
   float* xT = stash + L.xT + (size_t)t * RT * D_INP * 32;
@@ -2177,7 +2073,7 @@ static int chain_decoder_step(const ha_humor_net* net, const StashLayout& L, int
   g.Gs_next = sp + L.per_step + L.off_G;
   g.t2j = stash + L.t2j;
   g.world = world;
-  launch_glue_fwd(net->rotw, net->delta, RT * 32, st, g);
+  launch_glue_fwd(net->rotw, net->delta, RT * 32, st, g, fb);
   HA_LAUNCH_CHECK();
   return HA_OK;
 }
@@ -2279,6 +2175,87 @@ extern "C" int ha_humor_rollout_sample(const ha_humor_net* net, int B, int S, co
     g.pri_out = sp_.pri_out; g.pri_nsplit = sp_.pri_nsplit; g.pri_pad = sp_.pri_pad;
     g.prior_mu = prior_mu; g.prior_var = prior_var;
     int rc = chain_decoder_step(net, L, B, S, t, stash, world, false, g, st);
+    if (rc != HA_OK) return rc;
+  }
+  return HA_OK;
+}
+
+// Roll-out with SMPL-joint feedback (HumorModel(model_use_smpl_joint_inputs=True).roll_out(gender=, betas=), humor_model.py:894-954) on the
+// launch chain, forward only.  Per step: the prior layers (when the latent or the prior outputs need them), the latent, the decoder layers,
+// and glue_fwd_fb_kernel in the place of the plain glue -- no launch more than ha_humor_rollout_sample makes.
+extern "C" int ha_humor_rollout_smpl_joints(const ha_humor_net* net, int B, int S, const float* past_in0, const float* z_seq, const float* eps_seq,
+                                            const float* rest_joints, const int32_t* parents, float* world, float* prior_mu, float* prior_var,
+                                            float* z_out, float* stash, void* stream) {
+  HA_REQUIRE(net && past_in0 && rest_joints && parents && world && stash, "ha_humor_rollout_smpl_joints: null argument");
+  HA_REQUIRE(B >= 1 && S >= 1, "ha_humor_rollout_smpl_joints: B and S must be >= 1");
+  HA_REQUIRE(net->rotw == 3 && net->delta, "ha_humor_rollout_smpl_joints: built for out_rot_rep='aa' with output_delta=True only");
+  HA_REQUIRE((prior_mu == nullptr) == (prior_var == nullptr), "ha_humor_rollout_smpl_joints: prior_mu and prior_var go together");
+  HA_REQUIRE(!(z_seq && eps_seq), "ha_humor_rollout_smpl_joints: z_seq and eps_seq exclude each other");
+  HA_REQUIRE(z_seq || z_out, "ha_humor_rollout_smpl_joints: the sampling modes need z_out");
+  GlueFeedback fb;
+  memset(&fb, 0, sizeof(fb));
+  // kinematic tree of the 22 joints: parents[0] is the root's (ignored), 0 <= parents[j] < j; ancestors at distance 2^r, 5 bits each
+  int anc[NJT], depth[NJT], maxd = 0;
+  anc[0] = -1; depth[0] = 0;
+  for (int j = 1; j < NJT; ++j) {
+    HA_REQUIRE(parents[j] >= 0 && parents[j] < j, "ha_humor_rollout_smpl_joints: parents[%d]=%d must satisfy 0<=p<j", j, parents[j]);
+    anc[j] = parents[j];
+    depth[j] = depth[anc[j]] + 1;
+    maxd = std::max(maxd, depth[j]);
+  }
+  while ((1 << fb.nrounds) <= maxd) ++fb.nrounds;       // <= 5: maxd <= 21
+    for (int r = 0; r < 5; ++r) {
+    for (int j = 0; j < NJT; ++j) fb.anc[j] |= (anc[j] < 0 ? 31 : anc[j]) << (5 * r);
+    int nxt[NJT];
+    for (int j = 0; j < NJT; ++j) nxt[j] = anc[j] < 0 ? -1 : anc[anc[j]];
+    for (int j = 0; j < NJT; ++j) anc[j] = nxt[j];
+  }
+  fb.rest = rest_joints;
+
+  DeviceGuard guard(net->device);
+  hipStream_t st = (hipStream_t)stream;
+  StashLayout L;
+  make_layout(net, B, S, Path::chain, L);       // as the sampling roll-out: the launch chain, one group
+  const int RT = L.RT, rows = RT * 32;
+  float* x0 = stash + L.xT;
+  HA_LAUNCH(transpose_in_kernel, dim3(64), dim3(256), 0, st, past_in0, x0, B, 1, D_IN, D_INP, RT);
+  HA_LAUNCH_CHECK();
+  HA_LAUNCH(init_state_kernel, dim3(ceil_div(rows, 64)), dim3(64), 0, st, past_in0, stash + L.steps + L.off_G, stash + L.t2j, B, rows);
+  HA_LAUNCH_CHECK();
+  if (z_seq) {
+    HA_LAUNCH(transpose_in_kernel, dim3(256), dim3(256), 0, st, z_seq, stash + L.zT, B, S, ZD, ZD, RT);
+    HA_LAUNCH_CHECK();
+    if (z_out && z_out != z_seq) HA_CHECK_HIP(hipMemcpyAsync(z_out, z_seq, sizeof(float) * (size_t)B * S * ZD, hipMemcpyDeviceToDevice, st));
+  }
+  const int np = net->n_pri;
+  const bool run_prior = !z_seq || prior_mu;
+  for (int t = 0; t < S; ++t) {
+    GlueParams g;
+    memset(&g, 0, sizeof(g));
+    if (run_prior) {
+      // the states feed back through the body model: the prior of step t has to run on the recurrence, as in the sampling roll-out
+      for (int l = 0; l < np; ++l) {
+        LayerLaunch LL;
+        memset(&LL, 0, sizeof(LL));
+        LL.RT = RT;
+        const float* src = l == 0 ? x0 + (size_t)t * RT * D_INP * 32 : stash + L.smp_pri[l - 1];
+        fwd_task(LL.t[LL.ntasks++], net->pri[l], src, l == 0 ? 1 : L.nsf_pri[l - 1], nullptr, stash + L.smp_pri[l], L.nsf_pri[l]);
+        int rc = launch_layers(LL, L, stash, st);
+        if (rc != HA_OK) return rc;
+      }
+      g.pri_out = stash + L.smp_pri[np - 1]; g.pri_nsplit = L.nsf_pri[np - 1]; g.pri_pad = net->pri[np - 1].Nout_pad;
+      g.prior_mu = prior_mu; g.prior_var = prior_var;
+    }
+    if (!z_seq) {
+      SampleParams sp_;
+      memset(&sp_, 0, sizeof(sp_));
+      sp_.B = B; sp_.S = S; sp_.t = t; sp_.RT = RT;
+      sp_.pri_out = g.pri_out; sp_.pri_nsplit = g.pri_nsplit; sp_.pri_pad = g.pri_pad;
+      sp_.eps = eps_seq; sp_.zT_t = stash + L.zT + (size_t)t * RT * ZD * 32; sp_.z_out = z_out;
+      HA_LAUNCH(sample_z_kernel, dim3(rows), dim3(64), 0, st, sp_);
+      HA_LAUNCH_CHECK();
+    }
+    int rc = chain_decoder_step(net, L, B, S, t, stash, world, false, g, st, &fb);
     if (rc != HA_OK) return rc;
   }
   return HA_OK;

@@ -12,11 +12,17 @@ output_delta=False (the decoder emits the state itself, :331-347); these take th
 built for the residual 216-wide decoder.
 The INPUT variants -- in_rot_rep 'aa' / '6d' (:462-478, 970-981) and steps_in > 1 (:838-850, 946-957) -- are off the fitting path (the released
 checkpoint is 'mat' / 1): roll_out serves them with a step loop of on-device PyTorch operations (_roll_out_generic: prior through the fused MLP
-kernels, decoder through its module), pinned to reference fixtures (tests/golden/rollout_inrep.npz).  model_use_smpl_joint_inputs (a training-time
-option that needs one SMPL model file per gender) raises NotImplementedError.
+kernels, decoder through its module), pinned to reference fixtures (tests/golden/rollout_inrep.npz).
+
+model_use_smpl_joint_inputs (the HuMoR-Qual checkpoint: every roll-out step feeds the next one the SMPL+H joints of its own prediction,
+humor_model.py:210-227, 894-954) is built forward only, on the launch chain (ha_humor_rollout_smpl_joints: the 22-joint kinematic chain runs
+inside the step's glue launch).  It needs one SMPL+H model file per gender: pass their directory as ``smplh_path=``.  The bare flag raises
+NotImplementedError -- the reference's implicit ./body_models/smplh lookup is not provided.
 """
 import ctypes as C
+import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -168,6 +174,32 @@ class _RolloutFunction(torch.autograd.Function):
         return g_past, g_z, None, None, None
 
 
+GENDERS = ['male', 'female', 'neutral']      # the order the reference walks the gender groups in (humor_model.py:906)
+
+
+def _rollout_smpl_joints(handle, past_in, z_seq, eps, S, rest_joints, parents, want_prior):
+    """Roll-out with SMPL-joint feedback through ha_humor_rollout_smpl_joints (no autograd).  z_seq given, or sampled with eps
+    (None: the prior mean)."""
+    lib = handle.lib
+    past_in = past_in.contiguous().float()
+    B, dev = past_in.shape[0], past_in.device
+    n = C.c_int64()
+    lib.call('ha_humor_rollout_workspace', handle.ptr, B, S, C.byref(n))
+    stash = torch.empty(n.value, dtype=torch.float32, device=dev)
+    new = lambda d: torch.empty(B, S, d, dtype=torch.float32, device=dev)
+    world = new(348)
+    pm, pv = (new(48), new(48)) if (want_prior or z_seq is None) else (None, None)
+    z_seq = None if z_seq is None else z_seq.contiguous().float()
+    z_out = new(48) if z_seq is None else None
+    eps = None if eps is None else eps.contiguous().float()
+    rest_joints = rest_joints.contiguous().float()
+    assert rest_joints.shape == (B, 22, 3) and len(parents) == 22
+    par = (C.c_int32 * 22)(*[int(v) for v in parents])
+    lib.call('ha_humor_rollout_smpl_joints', handle.ptr, B, S, _lib.ptr(past_in), _lib.ptr(z_seq), _lib.ptr(eps), _lib.ptr(rest_joints), par,
+             _lib.ptr(world), _lib.ptr(pm), _lib.ptr(pv), _lib.ptr(z_out), _lib.ptr(stash), _lib.stream_ptr(past_in))
+    return world, pm, pv, (z_seq if z_out is None else z_out)
+
+
 def _rollout_sample(handle, past_in, eps, S):
     """Sampling roll-out through ha_humor_rollout_sample (no autograd)."""
     lib = handle.lib
@@ -189,7 +221,7 @@ class HumorModel(nn.Module):
     def __init__(self, in_rot_rep='aa', out_rot_rep='aa', latent_size=48, steps_in=1, conditional_prior=True,
                  output_delta=True, posterior_arch='mlp', decoder_arch='mlp', prior_arch='mlp',
                  model_data_config='smpl+joints+contacts', detach_sched_samp=True, model_use_smpl_joint_inputs=False,
-                 model_smpl_batch_size=1, _lib_override=None):
+                 model_smpl_batch_size=1, smplh_path=None, _lib_override=None):
         super(HumorModel, self).__init__()
         if out_rot_rep not in OUT_ROT_REPS:
             raise Exception('Not a valid output rotation representation: %s' % (out_rot_rep))
@@ -197,9 +229,12 @@ class HumorModel(nn.Module):
             raise Exception('Not a valid input rotation representation: %s' % (in_rot_rep))
         if 'mlp' not in (posterior_arch, decoder_arch, prior_arch) or {posterior_arch, decoder_arch, prior_arch} != {'mlp'}:
             raise Exception('Only mlp architectures exist')
-        if model_use_smpl_joint_inputs:
-            raise NotImplementedError('model_use_smpl_joint_inputs is a training-time option outside the fitting path')
-        self.ignore_keys = []
+        if model_use_smpl_joint_inputs and smplh_path is None:
+            raise NotImplementedError("model_use_smpl_joint_inputs needs the SMPL+H model files: the reference's implicit lookup of "
+                                      "./body_models/smplh is not provided -- pass smplh_path=<directory holding "
+                                      "male|female|neutral/model.npz>")
+        # the reference's body-model sub-modules: their checkpoint keys are dropped on load (humor_model.py:228)
+        self.ignore_keys = ['male_bm', 'female_bm', 'neutral_bm'] if model_use_smpl_joint_inputs else []
         self.steps_in, self.steps_out, self.out_step_size = steps_in, 1, 1
         self.detach_sched_samp = detach_sched_samp
         self.output_delta = output_delta
@@ -231,8 +266,11 @@ class HumorModel(nn.Module):
         self.use_conditional_prior = conditional_prior
         if conditional_prior:
             self.prior_net = MLP([past_dim, 1024, 1024, 1024, 1024, latent_size * 2])
-        self.use_smpl_joint_inputs = False
+        self.use_smpl_joint_inputs = bool(model_use_smpl_joint_inputs)
         self.smpl_batch_size = model_smpl_batch_size
+        self.smplh_path = smplh_path
+        self._body_models = {}      # (gender, device type, device index) -> BodyModel, created on first use
+        self._kintrees = {}         # gender -> parents of the first 22 joints
         self._lib = _lib_override
         self._net_handles = {}
         self._plists = {}           # parameter lists by sub-network name (None = all): walking the module tree costs ~0.15 ms per roll_out
@@ -249,9 +287,12 @@ class HumorModel(nn.Module):
         self._plists = {}
         return super()._apply(fn, *args, **kwargs)
 
-    def load_state_dict(self, *args, **kwargs):
+    def load_state_dict(self, state_dict, *args, **kwargs):
         self._plists = {}
-        return super().load_state_dict(*args, **kwargs)
+        if self.ignore_keys:
+            # a HuMoR-Qual checkpoint carries the buffers of its three body models; they are read from smplh_path here
+            state_dict = {k: v for k, v in state_dict.items() if k.split('.')[0] not in self.ignore_keys}
+        return super().load_state_dict(state_dict, *args, **kwargs)
 
     # ------------------------------------------------------------------------------------------------
     # single-step API (off the hot path; the prior / posterior MLPs run through ha_mlp_* on a HIP device)
@@ -423,17 +464,34 @@ class HumorModel(nn.Module):
         return out
 
     def prepare_input(self, data_in, device, data_out=None, return_input_dict=False, return_global_dict=False):
-        """Concatenates per-key data [B,T,...] into x_past [B,T,steps_in,D] (humor_model.py:233-314, input side)."""
-        if data_out is not None or return_global_dict:
-            raise NotImplementedError('training-side prepare_input (data_out / global dict) is outside the fitting path')
-        parts = []
-        for k in self.data_names:
-            cur = data_in[k].to(device)
-            parts.append(cur.reshape(cur.size(0), cur.size(1), self.steps_in, -1))
-        x_past = torch.cat(parts, dim=3)
+        """Concatenates per-key data [B,T,...] into x_past [B,T,steps_in,D] and, with data_out, x_t [B,T,steps_out,D] plus the dictionary of
+        ground-truth outputs (humor_model.py:230-314).  Returns x_past | (x_past, input_dict) without data_out; with it
+        (x_past, x_t, gt_dict[, input_dict][, global_gt_dict]): the global_* entries of data_out expanded to gt_dict's shapes."""
+        def gather(src, names, steps, prefix=''):
+            out = {}
+            for k in names:
+                cur = src[prefix + k].to(device)
+                out[k] = cur.reshape(cur.size(0), cur.size(1), steps, -1)
+            return out
+        parts = gather(data_in, self.data_names, self.steps_in)
+        x_past = torch.cat([parts[k] for k in self.data_names], dim=3)
+        input_dict = None
         if return_input_dict:
-            return x_past, {k: v for k, v in zip(self.data_names, parts)}
-        return x_past
+            input_dict = dict(parts)
+            input_dict.update(gather(data_in, self.aux_in_data_names or [], self.steps_in))
+        if data_out is None:
+            return (x_past, input_dict) if return_input_dict else x_past
+        gt_dict = gather(data_out, self.data_names, self.steps_out)
+        x_t = torch.cat([gt_dict[k] for k in self.data_names], dim=3)
+        gt_dict.update(gather(data_out, self.aux_out_data_names or [], self.steps_out))
+        ret = [x_past, x_t, gt_dict]
+        if return_input_dict:
+            ret.append(input_dict)
+        if return_global_dict:
+            # [B, T, ..., D] -> one copy per output step
+            glob = gather(data_out, self.data_names + (self.aux_out_data_names or []), 1, prefix='global_')
+            ret.append({k: v.expand_as(gt_dict[k]) for k, v in glob.items()})
+        return tuple(ret)
 
     # ------------------------------------------------------------------------------------------------
     # roll-out (hot path)
@@ -493,6 +551,10 @@ class HumorModel(nn.Module):
         (use_mean: z_t = mu_t; forward only).  eps_seq [B,S,48] is an extension for reproducible sampling (default: randn).
         Returns a dict of world-frame [B, num_steps, D] tensors (rotations as matrices), optionally (prior mean, var).
         '''
+        feedback = self.use_smpl_joint_inputs and gender is not None and betas is not None     # (humor_model.py:896)
+        if feedback and (self.in_rot_rep != 'mat' or self.steps_in != 1 or self.out_rot_rep != 'aa' or not self.output_delta):
+            raise NotImplementedError("SMPL-joint feedback is built for the released configuration only: in_rot_rep='mat', steps_in=1, "
+                                      "out_rot_rep='aa', output_delta=True")
         if self.in_rot_rep != 'mat' or self.steps_in != 1:
             return self._roll_out_generic(x_past, init_input_dict, num_steps, use_mean, z_seq, return_prior, return_z, canonicalize_input,
                                           uncanonicalize_output, eps_seq)
@@ -511,7 +573,22 @@ class HumorModel(nn.Module):
             past_in, uncanon = canonicalize_state(past_in)
         handle = self._net_handle(past_in.device)
         z_out = None
-        if z_seq is None:
+        if feedback:
+            # forward only (the reference never fits with this option)
+            if torch.is_grad_enabled() and (past_in.requires_grad or (z_seq is not None and z_seq.requires_grad)):
+                raise NotImplementedError('roll_out with SMPL-joint feedback is forward only: call it under torch.no_grad() or detach the '
+                                          'initial state and z_seq')
+            rest, parents = self._rest_joints(gender, betas, past_in.device)
+            if z_seq is not None:
+                eps, z_seq = None, z_seq[:, :num_steps].detach()
+            elif use_mean:
+                eps = None
+            elif eps_seq is not None:
+                eps = eps_seq[:, :num_steps]
+            else:
+                eps = torch.randn(B, num_steps, self.latent_size, device=past_in.device)
+            world, pm, pv, z_out = _rollout_smpl_joints(handle, past_in.detach(), z_seq, eps, num_steps, rest, parents, bool(return_prior))
+        elif z_seq is None:
             # sampling from the conditional prior (or its mean): forward only
             if use_mean:
                 eps = None
@@ -546,6 +623,48 @@ class HumorModel(nn.Module):
         if return_prior:
             return out, (pm, pv)
         return out
+
+    def _body_model(self, g, device):
+        """The SMPL+H model of gender `g` on `device`, created on first use."""
+        from .body_model import BodyModel
+        key = (g, device.type, device.index)
+        bm = self._body_models.get(key)
+        if bm is None:
+            path = os.path.join(self.smplh_path, g, 'model.npz')
+            # (joints only: the subset evaluation with a single vertex instead of the 6890 of the dense one)
+            bm = self._body_models[key] = BodyModel(bm_path=path, num_betas=16, batch_size=self.smpl_batch_size, vertex_subset=[0],
+                                                    _lib_override=self._lib)
+            kt = np.asarray(np.load(path, encoding='latin1', allow_pickle=True)['kintree_table'])[0][:NUM_SMPL_JOINTS]
+            self._kintrees[g] = [-1] + [int(v) for v in kt[1:]]
+        return bm
+
+    def _rest_joints(self, gender, betas, device):
+        """Rest joints J(betas) [B, 22, 3] of every sequence from its gender's body model (zero pose, zero translation: they are fixed for
+        the whole roll-out) and the kinematic tree of the 22 joints.  A gender group larger than model_smpl_batch_size raises as the
+        reference does (humor_model.py:919-925)."""
+        B = betas.size(0)
+        if len(gender) != B:
+            raise ValueError(f'roll_out: gender has {len(gender)} entries for a batch of {B}')
+        unknown = sorted(set(gender) - set(GENDERS))
+        if unknown:
+            raise ValueError(f"roll_out: gender entries must be 'male', 'female' or 'neutral', got {unknown}")
+        b0 = betas[:, 0, :].detach().to(device).float()
+        rest = torch.zeros(B, NUM_SMPL_JOINTS, 3, dtype=torch.float32, device=device)
+        parents = None
+        for g in GENDERS:
+            idx = [i for i, name in enumerate(gender) if name == g]
+            if not idx:
+                continue
+            if len(idx) > self.smpl_batch_size:
+                raise Exception('SMPL model batch size not large enough to accomodate!')
+            bm = self._body_model(g, device)
+            if parents is None:
+                parents = self._kintrees[g]
+            assert self._kintrees[g] == parents, f"the '{g}' body model's kinematic tree differs from the other genders'"
+            sel = torch.tensor(idx, dtype=torch.long, device=device)
+            with torch.no_grad():
+                rest[sel] = bm(betas=b0[sel]).Jtr[:, :NUM_SMPL_JOINTS]
+        return rest, parents
 
     def _window_as_input(self, win):
         """Window {name: [B, S, d]} (rotations as matrices) -> past_in [B, S * D_in] with the rotations in in_rot_rep (humor_model.py:970-981:

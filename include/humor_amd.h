@@ -30,7 +30,7 @@ extern "C" {
 #define HA_ERR_UNSUPPORTED 3   /* valid request this build cannot serve */
 
 const char* ha_last_error(void);
-/* ABI version of this header; bumped on any signature change. */
+/* ABI version of this header (4: + ha_humor_rollout_smpl_joints); bumped on any signature change or addition. */
 int ha_abi_version(void);
 /* Writes the device's gcnArchName (e.g. "gfx950:sramecc+:xnack-") into buf. */
 int ha_device_arch(int device, char* buf, int buflen);
@@ -212,6 +212,21 @@ int ha_humor_rollout_forward(const ha_humor_net* net, int B, int S, const float*
  * Outputs as ha_humor_rollout_forward plus the sampled latents z_out [B,S,48].  Forward only. */
 int ha_humor_rollout_sample(const ha_humor_net* net, int B, int S, const float* past_in0, const float* eps_seq,
                             float* world, float* prior_mu, float* prior_var, float* z_out, float* stash, void* stream);
+
+/* Roll-out with SMPL-joint feedback (HumorModel(model_use_smpl_joint_inputs=True).roll_out(gender=, betas=), humor_model.py:894-954;
+ * the HuMoR-Qual checkpoint): after every step the SMPL+H body model is posed with the step's own local-frame prediction and its first
+ * 22 joints replace the regressed joints in the NEXT input (the world outputs keep the regressed ones, joints_vel is not replaced).
+ * Those joints are forward kinematics over the 22 predicted rotations, each through the reference's matrix -> axis-angle -> matrix
+ * round trip, evaluated inside the step's glue launch: no launch is added to the step.
+ *   z_seq  [B,S,48] given latents, or NULL: z_t = prior_mu_t + eps_t * sqrt(prior_var_t) with eps_seq [B,S,48] (NULL = the prior mean)
+ *   rest_joints [B,22,3]  rest-pose joints J(betas) of every sequence's body model (device)
+ *   parents     [22]      HOST array, the kinematic tree: 0 <= parents[j] < j for j >= 1 (parents[0] is not read)
+ * outputs: world [B,S,348]; prior_mu / prior_var [B,S,48] (both or neither; NULL with a given z_seq skips the prior network);
+ * z_out [B,S,48] (required without z_seq, optional copy of it otherwise).  out_rot_rep='aa' with output_delta=1 only.  Forward only;
+ * stash sized by ha_humor_rollout_workspace. */
+int ha_humor_rollout_smpl_joints(const ha_humor_net* net, int B, int S, const float* past_in0, const float* z_seq, const float* eps_seq,
+                                 const float* rest_joints, const int32_t* parents, float* world, float* prior_mu, float* prior_var,
+                                 float* z_out, float* stash, void* stream);
 
 /* Backward roll-out: given gradients of the outputs, produce gradients of the inputs.
  *   g_world [B,S,348], g_prior_mu / g_prior_var [B,S,48] (NULL = zero)
