@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, 'csrc', 'libhumor_amd.so')
 
 HA_OK = 0
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int32)
@@ -116,6 +116,8 @@ _SIGS = {
     'ha_humor_rollout_forward': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]),
     'ha_humor_rollout_sample': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p]),
     'ha_humor_rollout_smpl_joints': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [c_int_p] + [C.c_void_p] * 5 + [C.c_void_p]),
+    'ha_humor_rollout_smpl_joints_fwd': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [c_int_p] + [C.c_void_p] * 4 + [C.c_void_p]),
+    'ha_humor_rollout_smpl_joints_bwd': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [c_int_p] + [C.c_void_p] * 8 + [C.c_void_p]),
     'ha_humor_rollout_backward': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p]),
     'ha_humor_net_set_option': (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     'ha_humor_persist_status': (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_int64)]),

@@ -123,7 +123,8 @@ struct ha_humor_net {
   // The plan of each forward call, keyed by the stash it filled, for the backward over that stash (one host thread per device: no lock).
   // A forward overwrites the record of its address and makes it the newest; beyond MAX_STASH_RECS records the oldest go first.
   // A backward leaves the record in place: a second backward over a retained graph finds it again.
-  struct StashRec { ha::CallPlan plan; int B, S, knobs; std::list<const void*>::iterator age; };
+  // feedback: filled by ha_humor_rollout_smpl_joints_fwd -- only ha_humor_rollout_smpl_joints_bwd may read it, and it reads no other
+  struct StashRec { ha::CallPlan plan; int B, S, knobs; bool feedback; std::list<const void*>::iterator age; };
   static constexpr size_t MAX_STASH_RECS = 65536;
   mutable std::unordered_map<const void*, StashRec> stash_recs;
   mutable std::list<const void*> stash_age;   // oldest first
@@ -825,6 +826,12 @@ struct GlueFeedback {
   int anc[NJT];             // joint j: its 2^r-th ancestor in bits [5r, 5r+5), 31 = none
 };
 
+// the adjoint of the feedback (glue_bwd_fb_kernel only)
+struct GlueFeedbackAdj {
+  float* g_rest;            // [B][22][3] dL/d(rest joints): zeroed once per backward call, lane (sequence, joint) adds its step's share
+  int sub[NJT];             // joint j: bit m set when m is in j's subtree (j itself included)
+};
+
 __device__ __forceinline__ float tsum(const float* base, int nsplit, int RT, int C, int rt, int c, int row) {
   return base ? slab_sum(base, nsplit, RT, C, rt, c, row) : 0.f;
 }
@@ -856,6 +863,9 @@ __device__ __forceinline__ void delta_rot_bwd(const float* raw, const float gR[9
 // round trips per lane.)
 constexpr int S_X = 0, S_RAW = 352, S_GXN = 704, S_GW = 1056, S_TOTAL = 1408;      // (the raw area holds up to RawLayout<9>::D = 348 channels)
 constexpr int S_SH = 1408, S_RED = 1424, S_TOTAL_BWD = 1456;   // + W(9) ptr(3) of the root | the joint wave's sums (27)
+// glue_bwd_fb_kernel, behind them: the 22 predicted rotations | the joint wave's chain [22][12] | the arriving joint gradients [22][3] |
+// dL/d(rest offsets) [22][3] | dL/d(predicted rotations) [22][9] (sRED[27..29]: their sum over the joints, for the predicted translation)
+constexpr int S_FB_ROT = 1456, S_FB_CH = 1656, S_FB_GAM = 1920, S_FB_DO = 1988, S_FB_GR = 2056, S_TOTAL_BWD_FB = 2256;
 
 template <int NQ, int NT = 64>   // NQ = ceil(channel quads / NT): thread l stages quads l, l + NT, ... (16-byte loads)
 __device__ __forceinline__ void stage_slabs(float* dst, const float* base, int nsplit, int RT, int C, int nch, int rt, int rr,
@@ -986,314 +996,25 @@ __device__ __forceinline__ void outer_acc(float M[9], const float a[3], const fl
 
 template <int ROTW, bool DELTA>
 __global__ __launch_bounds__(256) void glue_bwd_kernel(GlueParams p) {
-  using RL = RawLayout<ROTW>;
-  const int r = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int rt = r >> 5, rr = r & 31;
-  if (r >= p.B) return;
-  const bool last = p.t == p.S - 1;      // no step t+1 behind this one
-  const bool final_collect = p.t < 0;
+  constexpr bool FB = false;
+  const GlueFeedback fb = {};
+  const GlueFeedbackAdj fa = {};
+#include "glue_bwd_body.inc"
+}
 
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sX = smem + S_X;
-  float* sRAW = smem + S_RAW;
-  float* sGXN = smem + S_GXN;
-  float* sGW = smem + S_GW;
-  float* sSH = smem + S_SH;
-  float* sRED = smem + S_RED;
-  // ---- total adjoint of x_{t+1}: direct part + layer-0 input-gradient slabs of step t+1 (all 256 threads stage) -------
-  if (last) {
-    for (int c = tid; c < D_IN; c += 256) sGXN[c] = 0.f;
-  } else {
-    stage_slabs<1, 256>(sGXN, p.gx_dir_in, 1, p.RT, D_INP, D_IN, rt, rr, tid, false);
-    stage_slabs<1, 256>(sGXN, p.gxp_pri, p.gxp_pri_nsplit, p.RT, p.gxp_pri_pad, D_IN, rt, rr, tid, true);
-    stage_slabs<1, 256>(sGXN, p.gxp_dec, p.gxp_dec_nsplit, p.RT, p.gxp_dec_pad, D_IN, rt, rr, tid, true);
-  }
-  if (!final_collect) {
-    stage_slabs<1, 256>(sX, p.xT, 1, p.RT, D_INP, D_IN, rt, rr, tid, false);
-    stage_slabs<1, 256>(sRAW, p.dec_out, p.dec_nsplit, p.RT, p.dec_pad, RL::D, rt, rr, tid, false);
-    const float* GWp = p.g_world ? p.g_world + ((size_t)r * p.S + p.t) * D_STATE : nullptr;
-    for (int c = tid; c < D_STATE; c += 256) sGW[c] = GWp ? GWp[c] : 0.f;
-  }
-  // per-sequence state: issued before the barrier so that it overlaps the staging round trip
-  float* carry = p.carry + (size_t)r * 16;
-  float G[9], gt[3], t2j[3], gGn[9], ggtn[3], g_t2j_acc[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) { G[i] = 0.f; gGn[i] = 0.f; }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { gt[c] = 0.f; t2j[c] = 0.f; ggtn[c] = 0.f; g_t2j_acc[c] = 0.f; }
-  if (!final_collect && wave < 2) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) G[i] = p.Gs[(size_t)r * 12 + i];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { gt[c] = p.Gs[(size_t)r * 12 + 9 + c]; t2j[c] = p.t2j[(size_t)r * 3 + c]; }
-    if (!last && wave == 0) {
-      // incoming carried adjoints of (G', gt') = state after this step
-#pragma unroll
-      for (int i = 0; i < 9; ++i) gGn[i] = carry[i];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) { ggtn[c] = carry[9 + c]; g_t2j_acc[c] = carry[12 + c]; }
-    }
-  }
-  __syncthreads();
-  auto GXN = [&](int c) -> float { return sGXN[c]; };
-  auto gw = [&](int c) { return sGW[c]; };
-  if (final_collect) {
-    // dz of step 0 ; dL/dpast_in0 = adjoint of x_0 ; t2j = -(x0[207], x0[208], 0)
-    if (p.g_z && tid < ZD) {
-      float v = 0.f;
-      for (int i = 0; i < p.dz_n; ++i) v += slab_sum(p.dz_src[i], p.dz_nsplit[i], p.RT, p.dz_pad[i], rt, p.dz_off[i] + tid, rr);
-      p.g_z[((size_t)r * p.S + (p.t + 1)) * ZD + tid] = v;
-    }
-    for (int c = tid; c < D_IN; c += 256) {
-      float v = GXN(c);
-      if (c == 207) v -= carry[12];
-      if (c == 208) v -= carry[13];
-      p.g_past0[(size_t)r * D_IN + c] = v;
-    }
-    return;
-  }
-
-  float* GD = p.g_dec_out + (size_t)rt * p.dec_pad * 32 + (size_t)rr * 4;   // adjoint of the decoder raw output (quad layout)
-  float* GX = p.gx_dir_out + (size_t)rt * D_INP * 32 + (size_t)rr * 4;
-  PredState s;
-  W2A wa;
-  // lane-local partial sums of the adjoints shared by the whole sequence (W, G, gt, wt, t2j)
-  float gW[9], gG[9], ggt[3] = {0.f, 0.f, 0.f}, gwt[3] = {0.f, 0.f, 0.f}, gt2[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < 9; ++i) { gW[i] = 0.f; gG[i] = 0.f; }
-
-  // ---- phase 1 (before W is known) ---------------------------------------------------------------------
-  if (wave == 0) {
-    if (lane == 0) {
-      predict_root<ROTW, DELTA>(sX, sRAW, s);
-      w2a_fwd(s.pR, wa);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) sSH[i] = wa.W[i];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) sSH[9 + c] = s.ptrans[c];
-    }
-  } else if (wave == 1) {
-    if (lane < NJT) predict_joints<ROTW, DELTA>(sX, sRAW, lane, s);
-  } else if (wave == 2) {
-    // body rotation: pB = dB * Bin goes unchanged to both outputs (no dependence on W or G)
-    if (lane >= 1 && lane < NJT) {
-      const int bidx = lane - 1;
-      predict_body<ROTW, DELTA>(sX, sRAW, bidx, s);
-      float gpB[9], gdB[9], gBin[9], gaa[ROTW];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) gpB[i] = gw(18 + 9 * bidx + i) + GXN(18 + 9 * bidx + i);
-      if constexpr (DELTA) {
-        mat3_mult(gpB, s.Bin, gdB);      // gdB = gpB * Bin^T
-        mat3_tmul(s.dB, gpB, gBin);      // gBin = dB^T * gpB
-      } else {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) { gdB[i] = gpB[i]; gBin[i] = 0.f; }
-      }
-      delta_rot_bwd<ROTW>(s.raw_aa_b, gdB, gaa);
-#pragma unroll
-      for (int c = 0; c < ROTW; ++c) GD[qoff(RL::BODY + ROTW * bidx + c)] = gaa[c];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) GX[qoff(18 + 9 * bidx + i)] = gBin[i];
-    }
-  } else {
-    // dz of step t+1, contacts, padded decoder channels, prior output adjoint
-    if (!last && p.g_z && lane < ZD) {
-      float v = 0.f;
-      for (int i = 0; i < p.dz_n; ++i) v += slab_sum(p.dz_src[i], p.dz_nsplit[i], p.RT, p.dz_pad[i], rt, p.dz_off[i] + lane, rr);
-      p.g_z[((size_t)r * p.S + (p.t + 1)) * ZD + lane] = v;
-    }
-    if (lane >= 32 && lane < 32 + 9) GD[qoff(RL::CONT + lane - 32)] = gw(339 + lane - 32);
-    for (int c = RL::D + lane; c < p.dec_pad; c += 64) GD[qoff(c)] = 0.f;
-    if (p.g_pri_out) {
-      float* GP = p.g_pri_out + (size_t)rt * p.pri_pad * 32 + (size_t)rr * 4;
-      if (lane < ZD) {
-        const size_t o = ((size_t)r * p.S + p.t) * ZD + lane;
-        GP[qoff(lane)] = p.g_prior_mu ? p.g_prior_mu[o] : 0.f;
-        // var = exp(logvar): d/dlogvar = g_var * var (recomputed from the stashed prior output slabs)
-        const float var = expf(slab_sum(p.pri_out, p.pri_nsplit, p.RT, p.pri_pad, rt, ZD + lane, rr));
-        GP[qoff(ZD + lane)] = p.g_prior_var ? p.g_prior_var[o] * var : 0.f;
-      }
-      for (int c = 2 * ZD + lane; c < p.pri_pad; c += 64) GP[qoff(c)] = 0.f;
-    }
-  }
-  __syncthreads();
-  float W[9], ptr[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) W[i] = sSH[i];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) ptr[c] = sSH[9 + c];
-  const float wt[3] = {-ptr[0], -ptr[1], 0.f};
-
-  // ---- phase 2: joints (wave 1) next to the root (wave 0, lane 0) ----------------------------------------
-  float gptrans[3] = {0.f, 0.f, 0.f}, gptvel[3] = {0.f, 0.f, 0.f}, gprvel[3] = {0.f, 0.f, 0.f}, gpR[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) gpR[i] = 0.f;
-  if (wave == 1) {
-    if (lane < NJT) {
-      const int j = lane;
-    float g[3], q[3], o[3], gpj[3] = {0.f, 0.f, 0.f}, gjv[3] = {0.f, 0.f, 0.f};
-    // world joints: wj = G^T (pj + t2j) - t2j - gt
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { g[c] = gw(207 + 3 * j + c); q[c] = s.pj[c] + t2j[c]; }
-    mat3_vec(G, g, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { gpj[c] += o[c]; gt2[c] += o[c] - g[c]; ggt[c] -= g[c]; }
-    outer_acc(gG, q, g);
-    // world joint velocities: G^T jv
-#pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = gw(273 + 3 * j + c);
-    mat3_vec(G, g, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gjv[c] += o[c];
-    outer_acc(gG, s.jv, g);
-    // next-input joints: W (pj + wt + t2j) - t2j
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { g[c] = GXN(207 + 3 * j + c); q[c] = s.pj[c] + wt[c] + t2j[c]; }
-    mat3_tvec(W, g, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { gpj[c] += o[c]; gwt[c] += o[c]; gt2[c] += o[c] - g[c]; }
-    outer_acc(gW, g, q);
-    // next-input joint velocities: W jv
-#pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = GXN(273 + 3 * j + c);
-    mat3_tvec(W, g, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gjv[c] += o[c];
-    outer_acc(gW, g, s.jv);
-    // residual composition: pj = raw + x
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      GD[qoff(RL::JNT + 3 * j + c)] = gpj[c];
-      GX[qoff(207 + 3 * j + c)] = DELTA ? gpj[c] : 0.f;
-      GD[qoff(RL::JVEL + 3 * j + c)] = gjv[c];
-      GX[qoff(273 + 3 * j + c)] = DELTA ? gjv[c] : 0.f;
-    }
-    }
-    // reduce the joint lanes' partial sums and hand them to the root
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { gW[i] = wave_sum(gW[i]); gG[i] = wave_sum(gG[i]); }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { ggt[c] = wave_sum(ggt[c]); gwt[c] = wave_sum(gwt[c]); gt2[c] = wave_sum(gt2[c]); }
-    if (lane == 0) {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) { sRED[i] = gW[i]; sRED[9 + i] = gG[i]; }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) { sRED[18 + c] = ggt[c]; sRED[21 + c] = gwt[c]; sRED[24 + c] = gt2[c]; }
-    }
-  } else if (wave == 0 && lane == 0) {
-    float g[3], o[3], q[3];
-    // carried: gt' = (-wtrans.x, -wtrans.y, 0)
-    float gwtr[3] = {gw(0) - ggtn[0], gw(1) - ggtn[1], gw(2)};
-    // wtrans = G^T ptrans - gt
-    mat3_vec(G, gwtr, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { gptrans[c] += o[c]; ggt[c] -= gwtr[c]; }
-    outer_acc(gG, s.ptrans, gwtr);
-    // wtvel = G^T ptvel
-#pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = gw(3 + c);
-    mat3_vec(G, g, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gptvel[c] += o[c];
-    outer_acc(gG, s.ptvel, g);
-    // wR = G^T pR : gpR += G gwR ; gG += pR gwR^T
-    float gwR[9], M[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gwR[i] = gw(6 + i);
-    mat3_mul(G, gwR, M);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gpR[i] += M[i];
-    mat3_mult(s.pR, gwR, M);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gG[i] += M[i];
-    // wrvel = G^T prvel
-#pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = gw(15 + c);
-    mat3_vec(G, g, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gprvel[c] += o[c];
-    outer_acc(gG, s.prvel, g);
-    // G' = G W : gG += gG' W^T ; gW += G^T gG'
-    mat3_mult(gGn, W, M);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gG[i] += M[i];
-    mat3_tmul(G, gGn, M);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gW[i] += M[i];
-    // next input: trans' = W (ptrans + wt)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { g[c] = GXN(c); q[c] = s.ptrans[c] + wt[c]; }
-    mat3_tvec(W, g, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { gptrans[c] += o[c]; gwt[c] += o[c]; }
-    outer_acc(gW, g, q);
-    // tvel' = W ptvel
-#pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = GXN(3 + c);
-    mat3_tvec(W, g, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gptvel[c] += o[c];
-    outer_acc(gW, g, s.ptvel);
-    // R' = W pR : gpR += W^T gR' ; gW += gR' pR^T
-    float gRn[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gRn[i] = GXN(6 + i);
-    mat3_tmul(W, gRn, M);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gpR[i] += M[i];
-    mat3_mult(gRn, s.pR, M);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gW[i] += M[i];
-    // rvel' = W prvel
-#pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = GXN(15 + c);
-    mat3_tvec(W, g, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gprvel[c] += o[c];
-    outer_acc(gW, g, s.prvel);
-  }
-  __syncthreads();
-
-  // ---- phase 3: the root finishes (heading alignment and root rotation adjoints, carried state) -------------
-  if (wave == 0 && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { gW[i] += sRED[i]; gG[i] += sRED[9 + i]; }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { ggt[c] += sRED[18 + c]; gwt[c] += sRED[21 + c]; gt2[c] += sRED[24 + c]; }
-    // wt = (-ptrans.x, -ptrans.y, 0)
-    gptrans[0] -= gwt[0];
-    gptrans[1] -= gwt[1];
-    // W = world2aligned(pR)
-    float g0, g3;
-    w2a_bwd(wa, gW, g0, g3);
-    gpR[0] += g0;
-    gpR[3] += g3;
-    // pR = dR * Rin
-    float gdR[9], gRin[9], gaa[ROTW];
-    if constexpr (DELTA) {
-      mat3_mult(gpR, s.Rin, gdR);
-      mat3_tmul(s.dR, gpR, gRin);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) { gdR[i] = gpR[i]; gRin[i] = 0.f; }
-    }
-    delta_rot_bwd<ROTW>(s.raw_aa_r, gdR, gaa);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      GD[qoff(c)] = gptrans[c];        GX[qoff(c)] = DELTA ? gptrans[c] : 0.f;
-      GD[qoff(3 + c)] = gptvel[c];   GX[qoff(3 + c)] = DELTA ? gptvel[c] : 0.f;
-      GD[qoff(RL::RVEL + c)] = gprvel[c];   GX[qoff(15 + c)] = DELTA ? gprvel[c] : 0.f;
-    }
-#pragma unroll
-    for (int c = 0; c < ROTW; ++c) GD[qoff(RL::ROOT + c)] = gaa[c];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) GX[qoff(6 + i)] = gRin[i];
-    // carry to step t-1
-#pragma unroll
-    for (int i = 0; i < 9; ++i) carry[i] = gG[i];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { carry[9 + c] = ggt[c]; carry[12 + c] = g_t2j_acc[c] + gt2[c]; }
-  }
+// The adjoint of glue_fwd_fb_kernel (the released configuration only, as the forward).  With R_j the predicted rotations, a_j = rotmat_to_aa(R_j),
+// Q_j = rodrigues(a_j), o_j the rest offsets, A_j = A_parent(j) Q_j and p_j = p_parent(j) + A_parent(j) o_j the chain, and gamma_j the gradient
+// arriving on fb_j = p_j + ptrans from the joints slots of dL/dx_{t+1}:
+//   P_j = sum_{m in subtree(j)} gamma_m             dL/do_j = A_parent(j)^T P_j
+//   S_j = sum_{m in subtree(j)} gamma_m (p_m - p_j)^T      dL/dQ_j = A_parent(j)^T S_j A_j
+// (S_j is the issue's recursion M_j = sum_children (P_c o_c^T + M_c Q_c^T) rolled out: M_j = S_j A_j.)  The joint wave recomputes the chain as the
+// forward does, runs both sums over its subtree mask in ascending joint order out of LDS (one owner per sum, no atomics), takes dL/dQ_j through
+// rodrigues_bwd and rotmat_to_aa_bwd and leaves dL/dR_j in LDS; the root and the body-rotation wave add it to dL/dpR / dL/dpB behind the kernel's
+// last barrier, before delta_rot_bwd.  The regressed joints keep the world outputs' gradient only.
+__global__ __launch_bounds__(256) void glue_bwd_fb_kernel(GlueParams p, GlueFeedback fb, GlueFeedbackAdj fa) {
+  constexpr int ROTW = 3;
+  constexpr bool DELTA = true, FB = true;
+#include "glue_bwd_body.inc"
 }
 
 static inline void launch_glue_fwd(int rotw, bool delta, int rows, hipStream_t st, const GlueParams& g, const GlueFeedback* fb = nullptr) {
@@ -1307,7 +1028,12 @@ static inline void launch_glue_fwd(int rotw, bool delta, int rows, hipStream_t s
   else { if (rotw == 3) HA_GLUE_FWD(3, false); else if (rotw == 6) HA_GLUE_FWD(6, false); else HA_GLUE_FWD(9, false); }
 #undef HA_GLUE_FWD
 }
-static inline void launch_glue_bwd(int rotw, bool delta, int rows, hipStream_t st, const GlueParams& g) {
+static inline void launch_glue_bwd(int rotw, bool delta, int rows, hipStream_t st, const GlueParams& g, const GlueFeedback* fb = nullptr,
+                                   const GlueFeedbackAdj* fa = nullptr) {
+  if (fb) {      // (the entry point has checked rotw == 3 && delta)
+    HA_LAUNCH(glue_bwd_fb_kernel, dim3(rows), dim3(256), S_TOTAL_BWD_FB * sizeof(float), st, g, *fb, *fa);
+    return;
+  }
   const size_t lds = S_TOTAL_BWD * sizeof(float);
 #define HA_GLUE_BWD(R, D) HA_LAUNCH((glue_bwd_kernel<R, D>), dim3(rows), dim3(256), lds, st, g)
   if (delta) { if (rotw == 3) HA_GLUE_BWD(3, true); else if (rotw == 6) HA_GLUE_BWD(6, true); else HA_GLUE_BWD(9, true); }
@@ -2079,7 +1805,8 @@ static int chain_decoder_step(const ha_humor_net* net, const StashLayout& L, int
 }
 
 static int rollout_forward_impl(const ha_humor_net* net, const CallPlan& plan, const StashLayout& L, int B, int S, const float* past_in0,
-                                const float* z_seq, float* world, float* prior_mu, float* prior_var, float* stash, hipStream_t st, int phase, int t) {
+                                const float* z_seq, float* world, float* prior_mu, float* prior_var, float* stash, hipStream_t st, int phase, int t,
+                                const GlueFeedback* fb = nullptr) {
   const int RT = L.RT, rows = RT * 32;
   auto step_ptr = [&](int t) { return stash + L.steps + (size_t)t * L.per_step; };
   auto x_ptr = [&](int t) { return stash + L.xT + (size_t)t * RT * D_INP * 32; };
@@ -2117,7 +1844,7 @@ static int rollout_forward_impl(const ha_humor_net* net, const CallPlan& plan, c
   if (phase == PH_STEP) {
     GlueParams g;
     memset(&g, 0, sizeof(g));
-    return chain_decoder_step(net, L, B, S, t, stash, world, L.hsum, g, st);
+    return chain_decoder_step(net, L, B, S, t, stash, world, L.hsum, g, st, fb);
   }
   if (prior_mu) {
     const bool fold = g_gemm_fold != 0 && net->pri[np - 1].Nout == 2 * ZD;
@@ -2279,7 +2006,8 @@ static int prior_adjoint_all(const ha_humor_net* net, const StashLayout& L, int 
 
 static int rollout_backward_impl(const ha_humor_net* net, const CallPlan& plan, const StashLayout& L, int B, int S, const float* g_world,
                                  const float* g_prior_mu, const float* g_prior_var, float* stash, float* g_past_in0,
-                                 float* g_z_seq, hipStream_t st, int phase, int t) {
+                                 float* g_z_seq, hipStream_t st, int phase, int t, const GlueFeedback* fb = nullptr,
+                                 const GlueFeedbackAdj* fa = nullptr) {
   const int RT = L.RT, rows = RT * 32;
   auto step_ptr = [&](int t) { return stash + L.steps + (size_t)t * L.per_step; };
   auto x_ptr = [&](int t) { return stash + L.xT + (size_t)t * RT * D_INP * 32; };
@@ -2348,7 +2076,7 @@ static int rollout_backward_impl(const ha_humor_net* net, const CallPlan& plan, 
   if (phase == PH_STEP) {
     GlueParams g;
     fill_glue(g, t);
-    launch_glue_bwd(net->rotw, net->delta, rows, st, g);
+    launch_glue_bwd(net->rotw, net->delta, rows, st, g, fb, fa);
     HA_LAUNCH_CHECK();
     float* sp = step_ptr(t);
     for (int l = nd - 1; l >= 0; --l) {
@@ -2453,6 +2181,21 @@ static int for_each_group(const ha_humor_net* net, const CallPlan& plan, int B, 
 
 }  // namespace ha
 
+// records the plan of a forward call for the backward over its stash (see ha_humor_net::stash_recs)
+static void record_stash(const ha_humor_net* net, const float* stash, const CallPlan& plan, int B, int S, bool feedback) {
+  auto it = net->stash_recs.find(stash);
+  if (it != net->stash_recs.end()) net->stash_age.splice(net->stash_age.end(), net->stash_age, it->second.age);
+  else {
+    if (net->stash_recs.size() >= ha_humor_net::MAX_STASH_RECS) {
+      net->stash_recs.erase(net->stash_age.front());
+      net->stash_age.pop_front();
+    }
+    it = net->stash_recs.emplace(stash, ha_humor_net::StashRec{}).first;
+    it->second.age = net->stash_age.insert(net->stash_age.end(), stash);
+  }
+  it->second.plan = plan; it->second.B = B; it->second.S = S; it->second.knobs = layout_knobs(); it->second.feedback = feedback;
+}
+
 extern "C" int ha_humor_rollout_forward(const ha_humor_net* net, int B, int S, const float* past_in0, const float* z_seq,
                                         float* world, float* prior_mu, float* prior_var, float* stash, void* stream) {
   HA_REQUIRE(net && past_in0 && z_seq && world && stash, "ha_humor_rollout_forward: null argument");
@@ -2466,18 +2209,7 @@ extern "C" int ha_humor_rollout_forward(const ha_humor_net* net, int B, int S, c
   }
   DeviceGuard guard(net->device);
   const CallPlan plan = rollout_plan(net, B, S);
-  // record the plan for the backward over this stash (see ha_humor_net::stash_recs)
-  auto it = net->stash_recs.find(stash);
-  if (it != net->stash_recs.end()) net->stash_age.splice(net->stash_age.end(), net->stash_age, it->second.age);
-  else {
-    if (net->stash_recs.size() >= ha_humor_net::MAX_STASH_RECS) {
-      net->stash_recs.erase(net->stash_age.front());
-      net->stash_age.pop_front();
-    }
-    it = net->stash_recs.emplace(stash, ha_humor_net::StashRec{}).first;
-    it->second.age = net->stash_age.insert(net->stash_age.end(), stash);
-  }
-  it->second.plan = plan; it->second.B = B; it->second.S = S; it->second.knobs = layout_knobs();
+  record_stash(net, stash, plan, B, S, false);
   return for_each_group(net, plan, B, S, false, (hipStream_t)stream, [&](int g, int r0, int rows, const StashLayout& L, hipStream_t st, int phase, int t) {
     const size_t r = (size_t)r0;
     return rollout_forward_impl(net, plan, L, rows, S, past_in0 + r * D_IN, z_seq + r * S * ZD, world + r * S * D_STATE,
@@ -2515,6 +2247,8 @@ extern "C" int ha_humor_rollout_backward_ex(const ha_humor_net* net, int B, int 
   HA_REQUIRE(it != net->stash_recs.end(), "ha_humor_rollout_backward: no forward call of this network has filled this stash");
   HA_REQUIRE(it->second.B == B && it->second.S == S, "ha_humor_rollout_backward: the stash was filled by a forward call of %d x %d, not %d x %d",
              it->second.B, it->second.S, B, S);
+  HA_REQUIRE(!it->second.feedback, "ha_humor_rollout_backward: this stash was filled by ha_humor_rollout_smpl_joints_fwd (SMPL-joint feedback): "
+             "its adjoint is ha_humor_rollout_smpl_joints_bwd");
   HA_REQUIRE(it->second.knobs == layout_knobs(), "ha_humor_rollout_backward: a layout knob (layer_finish / rollout_pipe / rollout_groups) changed "
              "between the forward call that filled this stash and its backward");
   CallPlan plan = it->second.plan;
@@ -2533,6 +2267,98 @@ extern "C" int ha_humor_rollout_backward_ex(const ha_humor_net* net, int B, int 
   if (rc == HA_OK && g_z_add && !plan.g_z_add) {
     const int n = B * S * ZD;
     HA_LAUNCH(add_inplace_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, g_z_seq, g_z_add, n);
+    HA_LAUNCH_CHECK();
+  }
+  return rc;
+}
+
+// ---- SMPL-joint feedback with gradients --------------------------------------------------------------
+// The kinematic tree of the 22 joints as the feedback glue kernels read it: ancestors at distance 2^r, five bits each, and every joint's subtree.
+static int make_feedback(const char* who, const int32_t* parents, const float* rest_joints, GlueFeedback& fb, GlueFeedbackAdj& fa) {
+  memset(&fb, 0, sizeof(fb));
+  memset(&fa, 0, sizeof(fa));
+  int anc[NJT], par[NJT], depth[NJT], maxd = 0;
+  anc[0] = par[0] = -1; depth[0] = 0;
+  for (int j = 1; j < NJT; ++j) {
+    HA_REQUIRE(parents[j] >= 0 && parents[j] < j, "%s: parents[%d]=%d must satisfy 0<=p<j", who, j, parents[j]);
+    anc[j] = par[j] = parents[j];
+    depth[j] = depth[anc[j]] + 1;
+    maxd = std::max(maxd, depth[j]);
+  }
+  while ((1 << fb.nrounds) <= maxd) ++fb.nrounds;       // <= 5: maxd <= 21
+  for (int r = 0; r < 5; ++r) {
+    for (int j = 0; j < NJT; ++j) fb.anc[j] |= (anc[j] < 0 ? 31 : anc[j]) << (5 * r);
+    int nxt[NJT];
+    for (int j = 0; j < NJT; ++j) nxt[j] = anc[j] < 0 ? -1 : anc[anc[j]];
+    for (int j = 0; j < NJT; ++j) anc[j] = nxt[j];
+  }
+  for (int m = 0; m < NJT; ++m)
+    for (int a = m; a >= 0; a = par[a]) fa.sub[a] |= 1 << m;
+  fb.rest = rest_joints;
+  return HA_OK;
+}
+
+// ha_humor_rollout_forward on the launch chain with the feedback glue: the whole batch as one group; with a given latent the prior is not on
+// the recurrence and runs once over the stashed states, which keeps its pre-activations for the adjoint.
+extern "C" int ha_humor_rollout_smpl_joints_fwd(const ha_humor_net* net, int B, int S, const float* past_in0, const float* z_seq,
+                                                const float* rest_joints, const int32_t* parents, float* world, float* prior_mu, float* prior_var,
+                                                float* stash, void* stream) {
+  HA_REQUIRE(net && past_in0 && z_seq && rest_joints && parents && world && stash, "ha_humor_rollout_smpl_joints_fwd: null argument");
+  HA_REQUIRE(B >= 1 && S >= 1, "ha_humor_rollout_smpl_joints_fwd: B and S must be >= 1");
+  HA_REQUIRE(net->rotw == 3 && net->delta, "ha_humor_rollout_smpl_joints_fwd: built for out_rot_rep='aa' with output_delta=True only");
+  HA_REQUIRE((prior_mu == nullptr) == (prior_var == nullptr), "ha_humor_rollout_smpl_joints_fwd: prior_mu and prior_var go together");
+  GlueFeedback fb;
+  GlueFeedbackAdj fa;
+  int rc = make_feedback("ha_humor_rollout_smpl_joints_fwd", parents, rest_joints, fb, fa);
+  if (rc != HA_OK) return rc;
+  DeviceGuard guard(net->device);
+  hipStream_t st = (hipStream_t)stream;
+  CallPlan plan;            // Path::chain, one group
+  plan.rows_per_group = ceil_div(B, 32) * 32;
+  StashLayout L;
+  make_layout(net, B, S, Path::chain, L);
+  record_stash(net, stash, plan, B, S, true);
+  rc = rollout_forward_impl(net, plan, L, B, S, past_in0, z_seq, world, prior_mu, prior_var, stash, st, PH_BEGIN, 0, &fb);
+  for (int t = 0; t < S && rc == HA_OK; ++t) rc = rollout_forward_impl(net, plan, L, B, S, past_in0, z_seq, world, prior_mu, prior_var, stash, st, PH_STEP, t, &fb);
+  if (rc == HA_OK) rc = rollout_forward_impl(net, plan, L, B, S, past_in0, z_seq, world, prior_mu, prior_var, stash, st, PH_END, 0, &fb);
+  return rc;
+}
+
+// ha_humor_rollout_backward_ex over a feedback stash: glue_bwd_fb_kernel in the place of the plain backward glue (no launch more per step), and
+// dL/d(rest joints) accumulated over the steps by the lane that owns (sequence, joint).
+extern "C" int ha_humor_rollout_smpl_joints_bwd(const ha_humor_net* net, int B, int S, const float* z_seq, const float* rest_joints,
+                                                const int32_t* parents, const float* g_world, const float* g_prior_mu, const float* g_prior_var,
+                                                float* stash, float* g_past_in0, float* g_z_seq, float* g_rest, const float* g_z_add, void* stream) {
+  HA_REQUIRE(net && rest_joints && parents && stash && g_past_in0 && g_z_seq && g_rest, "ha_humor_rollout_smpl_joints_bwd: null argument");
+  HA_REQUIRE(B >= 1 && S >= 1, "ha_humor_rollout_smpl_joints_bwd: B and S must be >= 1");
+  HA_REQUIRE(net->rotw == 3 && net->delta, "ha_humor_rollout_smpl_joints_bwd: built for out_rot_rep='aa' with output_delta=True only");
+  (void)z_seq;
+  const auto it = net->stash_recs.find(stash);
+  HA_REQUIRE(it != net->stash_recs.end(), "ha_humor_rollout_smpl_joints_bwd: no forward call of this network has filled this stash");
+  HA_REQUIRE(it->second.feedback, "ha_humor_rollout_smpl_joints_bwd: this stash was filled by a roll-out without SMPL-joint feedback: its adjoint is "
+             "ha_humor_rollout_backward");
+  HA_REQUIRE(it->second.B == B && it->second.S == S, "ha_humor_rollout_smpl_joints_bwd: the stash was filled by a forward call of %d x %d, not %d x %d",
+             it->second.B, it->second.S, B, S);
+  HA_REQUIRE(it->second.knobs == layout_knobs(), "ha_humor_rollout_smpl_joints_bwd: a layout knob (layer_finish / rollout_pipe / rollout_groups) changed "
+             "between the forward call that filled this stash and its backward");
+  const CallPlan plan = it->second.plan;
+  GlueFeedback fb;
+  GlueFeedbackAdj fa;
+  int rc = make_feedback("ha_humor_rollout_smpl_joints_bwd", parents, rest_joints, fb, fa);
+  if (rc != HA_OK) return rc;
+  fa.g_rest = g_rest;
+  DeviceGuard guard(net->device);
+  hipStream_t st = (hipStream_t)stream;
+  HA_CHECK_HIP(hipMemsetAsync(g_rest, 0, sizeof(float) * (size_t)B * NJT * 3, st));
+  StashLayout L;
+  make_layout(net, B, S, Path::chain, L);
+  rc = rollout_backward_impl(net, plan, L, B, S, g_world, g_prior_mu, g_prior_var, stash, g_past_in0, g_z_seq, st, PH_BEGIN, 0, &fb, &fa);
+  for (int t = S - 1; t >= 0 && rc == HA_OK; --t)
+    rc = rollout_backward_impl(net, plan, L, B, S, g_world, g_prior_mu, g_prior_var, stash, g_past_in0, g_z_seq, st, PH_STEP, t, &fb, &fa);
+  if (rc == HA_OK) rc = rollout_backward_impl(net, plan, L, B, S, g_world, g_prior_mu, g_prior_var, stash, g_past_in0, g_z_seq, st, PH_END, 0, &fb, &fa);
+  if (rc == HA_OK && g_z_add) {
+    const int n = B * S * ZD;
+    HA_LAUNCH(add_inplace_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, g_z_seq, g_z_add, n);
     HA_LAUNCH_CHECK();
   }
   return rc;

@@ -15,8 +15,10 @@ checkpoint is 'mat' / 1): roll_out serves them with a step loop of on-device PyT
 kernels, decoder through its module), pinned to reference fixtures (tests/golden/rollout_inrep.npz).
 
 model_use_smpl_joint_inputs (the HuMoR-Qual checkpoint: every roll-out step feeds the next one the SMPL+H joints of its own prediction,
-humor_model.py:210-227, 894-954) is built forward only, on the launch chain (ha_humor_rollout_smpl_joints: the 22-joint kinematic chain runs
-inside the step's glue launch).  It needs one SMPL+H model file per gender: pass their directory as ``smplh_path=``.  The bare flag raises
+humor_model.py:210-227, 894-954) runs on the launch chain (ha_humor_rollout_smpl_joints: the 22-joint kinematic chain runs inside the step's
+glue launch), forward only by default.  ``smpl_joint_gradients=True`` (ours) makes the given-z roll-out differentiable through the feedback
+(ha_humor_rollout_smpl_joints_fwd / _bwd: the chain's adjoint inside the step's backward glue launch) w.r.t. the initial state, z_seq and
+betas -- what a fit with that checkpoint needs (motion_optimizer.py:944-948).  It needs one SMPL+H model file per gender: pass their directory as ``smplh_path=``.  The bare flag raises
 NotImplementedError -- the reference's implicit ./body_models/smplh lookup is not provided.
 """
 import ctypes as C
@@ -174,6 +176,49 @@ class _RolloutFunction(torch.autograd.Function):
         return g_past, g_z, None, None, None
 
 
+class _RolloutSmplJointsFunction(torch.autograd.Function):
+    """(past_in0 [B,339], z_seq [B,S,48], rest_joints [B,22,3]) -> (world [B,S,348], prior_mu, prior_var [B,S,48]) with SMPL-joint feedback:
+    ha_humor_rollout_smpl_joints_fwd / _bwd (the launch chain with the feedback glue in both directions)."""
+
+    @staticmethod
+    def forward(ctx, past_in0, z_seq, rest_joints, handle, parents, want_prior, z_thru=False):
+        lib = handle.lib
+        z_in = z_seq
+        past_in0, z_seq, rest_joints = past_in0.contiguous().float(), z_seq.contiguous().float(), rest_joints.contiguous().float()
+        B, S = z_seq.shape[0], z_seq.shape[1]
+        assert rest_joints.shape == (B, 22, 3) and len(parents) == 22
+        dev = past_in0.device
+        n = C.c_int64()
+        lib.call('ha_humor_rollout_workspace', handle.ptr, B, S, C.byref(n))
+        stash = torch.empty(n.value, dtype=torch.float32, device=dev)
+        world = torch.empty(B, S, 348, dtype=torch.float32, device=dev)
+        pm = torch.empty(B, S, 48, dtype=torch.float32, device=dev) if want_prior else None
+        pv = torch.empty(B, S, 48, dtype=torch.float32, device=dev) if want_prior else None
+        par = (C.c_int32 * 22)(*[int(v) for v in parents])
+        lib.call('ha_humor_rollout_smpl_joints_fwd', handle.ptr, B, S, _lib.ptr(past_in0), _lib.ptr(z_seq), _lib.ptr(rest_joints), par,
+                 _lib.ptr(world), _lib.ptr(pm), _lib.ptr(pv), _lib.ptr(stash), _lib.stream_ptr(past_in0))
+        ctx.handle, ctx.stash, ctx.dims, ctx.par = handle, stash, (B, S), par
+        ctx.save_for_backward(z_seq, rest_joints)
+        ctx.set_materialize_grads(False)
+        return world, pm, pv, (z_in if z_thru else None)
+
+    @staticmethod
+    def backward(ctx, g_world, g_pm, g_pv, g_z_thru=None):
+        handle, (B, S) = ctx.handle, ctx.dims
+        lib = handle.lib
+        z_seq, rest_joints = ctx.saved_tensors
+        dev = z_seq.device
+        c = lambda t: None if t is None else t.contiguous().float()
+        g_world, g_pm, g_pv, g_z_thru = c(g_world), c(g_pm), c(g_pv), c(g_z_thru)
+        g_past = torch.empty(B, 339, dtype=torch.float32, device=dev)
+        g_z = torch.empty(B, S, 48, dtype=torch.float32, device=dev)
+        g_rest = torch.empty(B, 22, 3, dtype=torch.float32, device=dev)
+        lib.call('ha_humor_rollout_smpl_joints_bwd', handle.ptr, B, S, _lib.ptr(z_seq), _lib.ptr(rest_joints), ctx.par, _lib.ptr(g_world),
+                 _lib.ptr(g_pm), _lib.ptr(g_pv), _lib.ptr(ctx.stash), _lib.ptr(g_past), _lib.ptr(g_z), _lib.ptr(g_rest), _lib.ptr(g_z_thru),
+                 _lib.stream_ptr(z_seq))
+        return g_past, g_z, g_rest, None, None, None, None
+
+
 GENDERS = ['male', 'female', 'neutral']      # the order the reference walks the gender groups in (humor_model.py:906)
 
 
@@ -221,7 +266,7 @@ class HumorModel(nn.Module):
     def __init__(self, in_rot_rep='aa', out_rot_rep='aa', latent_size=48, steps_in=1, conditional_prior=True,
                  output_delta=True, posterior_arch='mlp', decoder_arch='mlp', prior_arch='mlp',
                  model_data_config='smpl+joints+contacts', detach_sched_samp=True, model_use_smpl_joint_inputs=False,
-                 model_smpl_batch_size=1, smplh_path=None, _lib_override=None):
+                 model_smpl_batch_size=1, smplh_path=None, smpl_joint_gradients=False, _lib_override=None):
         super(HumorModel, self).__init__()
         if out_rot_rep not in OUT_ROT_REPS:
             raise Exception('Not a valid output rotation representation: %s' % (out_rot_rep))
@@ -269,6 +314,9 @@ class HumorModel(nn.Module):
         self.use_smpl_joint_inputs = bool(model_use_smpl_joint_inputs)
         self.smpl_batch_size = model_smpl_batch_size
         self.smplh_path = smplh_path
+        # (ours, like smplh_path) roll_out with feedback and a given z_seq is differentiable w.r.t. the initial state, z_seq and betas
+        self.smpl_joint_gradients = bool(smpl_joint_gradients)
+        self._gender_rows = {}      # (gender tuple, device) -> per-gender row indices and the permutation back to batch order
         self._body_models = {}      # (gender, device type, device index) -> BodyModel, created on first use
         self._kintrees = {}         # gender -> parents of the first 22 joints
         self._lib = _lib_override
@@ -573,11 +621,22 @@ class HumorModel(nn.Module):
             past_in, uncanon = canonicalize_state(past_in)
         handle = self._net_handle(past_in.device)
         z_out = None
-        if feedback:
-            # forward only (the reference never fits with this option)
+        if feedback and self.smpl_joint_gradients and torch.is_grad_enabled() and z_seq is not None:
+            # the fitting path of the Qual checkpoint (motion_optimizer.py:944-948): gradients through the feedback into the initial state, the
+            # latents and -- through the rest joints and the body model's own adjoint -- betas
+            rest, parents = self._rest_joints(gender, betas, past_in.device, differentiable=True)
+            z_seq = z_seq[:, :num_steps]
+            world, pm, pv, z_t = _RolloutSmplJointsFunction.apply(past_in, z_seq, rest, handle, parents, bool(return_prior),
+                                                                  bool(return_world and return_z))
+            z_out = z_seq if z_t is None else z_t
+        elif feedback:
             if torch.is_grad_enabled() and (past_in.requires_grad or (z_seq is not None and z_seq.requires_grad)):
-                raise NotImplementedError('roll_out with SMPL-joint feedback is forward only: call it under torch.no_grad() or detach the '
-                                          'initial state and z_seq')
+                if self.smpl_joint_gradients:
+                    raise NotImplementedError('roll_out with SMPL-joint feedback differentiates with a given z_seq only: the sampling modes '
+                                              '(use_mean, eps_seq) are forward only -- call them under torch.no_grad() or detach the initial state')
+                raise NotImplementedError('roll_out with SMPL-joint feedback is forward only on this model: build it with '
+                                          'HumorModel(..., smpl_joint_gradients=True) to differentiate through the feedback (given z_seq), or call '
+                                          'it under torch.no_grad() / detach the initial state and z_seq')
             rest, parents = self._rest_joints(gender, betas, past_in.device)
             if z_seq is not None:
                 eps, z_seq = None, z_seq[:, :num_steps].detach()
@@ -638,32 +697,48 @@ class HumorModel(nn.Module):
             self._kintrees[g] = [-1] + [int(v) for v in kt[1:]]
         return bm
 
-    def _rest_joints(self, gender, betas, device):
+    def _rest_joints(self, gender, betas, device, differentiable=False):
         """Rest joints J(betas) [B, 22, 3] of every sequence from its gender's body model (zero pose, zero translation: they are fixed for
         the whole roll-out) and the kinematic tree of the 22 joints.  A gender group larger than model_smpl_batch_size raises as the
-        reference does (humor_model.py:919-925)."""
+        reference does (humor_model.py:919-925).  differentiable: the body model is evaluated with autograd on, so that dL/d(rest joints)
+        reaches betas through its own adjoint."""
         B = betas.size(0)
         if len(gender) != B:
             raise ValueError(f'roll_out: gender has {len(gender)} entries for a batch of {B}')
         unknown = sorted(set(gender) - set(GENDERS))
         if unknown:
             raise ValueError(f"roll_out: gender entries must be 'male', 'female' or 'neutral', got {unknown}")
-        b0 = betas[:, 0, :].detach().to(device).float()
-        rest = torch.zeros(B, NUM_SMPL_JOINTS, 3, dtype=torch.float32, device=device)
-        parents = None
-        for g in GENDERS:
-            idx = [i for i, name in enumerate(gender) if name == g]
-            if not idx:
-                continue
-            if len(idx) > self.smpl_batch_size:
-                raise Exception('SMPL model batch size not large enough to accomodate!')
-            bm = self._body_model(g, device)
-            if parents is None:
-                parents = self._kintrees[g]
-            assert self._kintrees[g] == parents, f"the '{g}' body model's kinematic tree differs from the other genders'"
-            sel = torch.tensor(idx, dtype=torch.long, device=device)
-            with torch.no_grad():
-                rest[sel] = bm(betas=b0[sel]).Jtr[:, :NUM_SMPL_JOINTS]
+        # the row indices of every gender group and the permutation from group order back to batch order, kept per (genders, device): a
+        # repeated call (every closure evaluation of a fit) copies nothing to the device
+        key = (tuple(gender), device.type, device.index)
+        rows = self._gender_rows.get(key)
+        if rows is None:
+            groups = [(g, [i for i, name in enumerate(gender) if name == g]) for g in GENDERS]
+            groups = [(g, idx) for g, idx in groups if idx]
+            order = [i for _, idx in groups for i in idx]
+            inv = [0] * B
+            for pos, i in enumerate(order):
+                inv[i] = pos
+            rows = ([(g, len(idx), torch.tensor(idx, dtype=torch.long, device=device)) for g, idx in groups],
+                    torch.tensor(inv, dtype=torch.long, device=device))
+            if len(self._gender_rows) >= 64:
+                self._gender_rows.clear()
+            self._gender_rows[key] = rows
+        groups, inv = rows
+        b0 = betas[:, 0, :].to(device).float()
+        if not differentiable:
+            b0 = b0.detach()
+        parents, parts = None, []
+        with torch.set_grad_enabled(differentiable and torch.is_grad_enabled()):
+            for g, n, sel in groups:
+                if n > self.smpl_batch_size:
+                    raise Exception('SMPL model batch size not large enough to accomodate!')
+                bm = self._body_model(g, device)
+                if parents is None:
+                    parents = self._kintrees[g]
+                assert self._kintrees[g] == parents, f"the '{g}' body model's kinematic tree differs from the other genders'"
+                parts.append(bm(betas=b0.index_select(0, sel)).Jtr[:, :NUM_SMPL_JOINTS])
+            rest = (parts[0] if len(parts) == 1 else torch.cat(parts, 0)).index_select(0, inv)
         return rest, parents
 
     def _window_as_input(self, win):

@@ -50,6 +50,8 @@ class MotionOptimizer():
         self.stage3_contact_refine_only = stage3_contact_refine_only
         self.im_dim = im_dim
         self.shard = shard
+        if shard is not None and getattr(motion_prior, 'use_smpl_joint_inputs', False):
+            raise NotImplementedError('MotionOptimizer: a sharded fit with an SMPL-joint feedback prior is not offered')
         self.verbose = verbose
         # whole-closure hipGraph capture (replay costs ~1.5 us of node hand-off per kernel, eager costs host time that the
         # roll-out's long launches partly hide: which one wins depends on the host -- bench.py times both)
@@ -216,11 +218,30 @@ class MotionOptimizer():
             halo['ov_next'] = min(self._pair_info['ov_next'], T)
         return halo
 
-    def make_closure(self, objective, params, optim=None, short=True):
+    def _feedback_prior(self):
+        """The motion prior feeds SMPL joints back (the HuMoR-Qual checkpoint): its roll-outs take the fit's gender and betas."""
+        return bool(getattr(self.motion_prior, 'use_smpl_joint_inputs', False))
+
+    def _feedback_kwargs(self, B, betas, fit_gender):
+        """gender= / betas= of a roll_out call (motion_optimizer.py:944-948); nothing for a plain prior."""
+        if not self._feedback_prior():
+            return {}
+        return dict(gender=[fit_gender] * B, betas=betas.reshape((B, 1, -1)))
+
+    def _check_feedback_prior(self):
+        if not self._feedback_prior():
+            return
+        if not getattr(self.motion_prior, 'smpl_joint_gradients', False):
+            raise ValueError('MotionOptimizer: the motion prior feeds SMPL joints back (model_use_smpl_joint_inputs) but was built forward only: '
+                             'stage 3 differentiates through the feedback -- build it with HumorModel(..., smpl_joint_gradients=True)')
+        if self.shard is not None:
+            raise NotImplementedError('MotionOptimizer: a sharded fit with an SMPL-joint feedback prior is not offered')
+
+    def make_closure(self, objective, params, optim=None, short=True, eager_only=False):
         """Returns the L-BFGS closure for `objective()` -> (loss, stats).  With use_graphs the objective and its backward are
         captured once into a hipGraph (torch.cuda.graphs) and replayed per evaluation; `short` marks the closures that
-        use_graphs='auto' captures (see __init__)."""
-        if not self.use_graphs or (self.use_graphs == 'auto' and not short):
+        use_graphs='auto' captures (see __init__); `eager_only` closures are never captured."""
+        if eager_only or not self.use_graphs or (self.use_graphs == 'auto' and not short):
             def closure():
                 for p in params:          # = optim.zero_grad(set_to_none=True) of the reference closures
                     p.grad = None
@@ -455,6 +476,7 @@ class MotionOptimizer():
                               'pose_body': self.latent2pose(self.latent_pose).clone().detach(), 'betas': self.betas.clone().detach()}
 
         # ---- Stage III set-up -------------------------------------------------------------------------
+        self._check_feedback_prior()
         self.fitting_loss.set_stage(2)
         og_overlap_w = self.fitting_loss.loss_weights['rgb_overlap_consist']
         motion_params, prior_opt_params = self.setup_stage3(data_fps)
@@ -523,7 +545,7 @@ class MotionOptimizer():
                 closures3[phase] = self.make_closure(
                     lambda tp=tune_phase, ims=init_motion_scale: self._stage3_objective(
                         obs_local, obs_init, prior_opt_params, tp, n_init, ims, og_overlap_w, has_overlap, fit_gender),
-                    motion_params, None, short=tune_phase)
+                    motion_params, None, short=tune_phase, eager_only=self._feedback_prior())
             motion_optim.step(closures3[phase])
             self._check_rollout_health()
             self._check_finite(motion_optim, phase_name, i)
@@ -692,7 +714,7 @@ class MotionOptimizer():
         return cfg
 
     def _stage3_objective_nodes(self, cfg, obs_local, obs_init, prior_opt_params, tune_phase, n_init, init_motion_scale, og_overlap_w,
-                                has_overlap):
+                                has_overlap, fit_gender='neutral'):
         """_stage3_objective as three composite autograd nodes + the fused loss (humor_amd/stage3.py): the same library calls in the same
         order, but no tensor with two readers crosses a node boundary, so autograd launches no accumulation kernels between them."""
         from .stage3 import Stage3Body, Stage3Head
@@ -720,8 +742,9 @@ class MotionOptimizer():
         latent_motion = L(self.latent_motion)
         if tune_phase:
             latent_motion = latent_motion[:, :(n_init - 1)]
+        # (a feedback prior reads the betas handed through the head, so that their gradients meet inside Stage3Head)
         res = self.motion_prior.roll_out(past_in.unsqueeze(1), None, latent_motion.size(1), z_seq=latent_motion, return_prior=self.cond_prior,
-                                         return_world=True, return_z=True)
+                                         return_world=True, return_z=True, **self._feedback_kwargs(B, betas_t, fit_gender))
         world, prior_out, z_t = res if self.cond_prior else (res[0], None, res[1])
         (pri_jtr, pri_verts, cam_jtr, cam_verts, r_trans, r_root, r_pose, ro_joints, conf, contacts, _cam_trans, _cam_root, betas_t) = Stage3Body.apply(
             cfg, world, trans_p, root_p, pose0, joints_p, c2p_R, c2p_t, betas_t)
@@ -751,7 +774,7 @@ class MotionOptimizer():
         cfg = self._stage3_nodes_config(self.trans)
         if cfg is not None:
             return self._stage3_objective_nodes(cfg, obs_local, obs_init, prior_opt_params, tune_phase, n_init, init_motion_scale, og_overlap_w,
-                                                has_overlap)
+                                                has_overlap, fit_gender)
         L = self._local
         trans, root_orient, betas = L(self.trans), L(self.root_orient), L(self.betas)
         floor = L(self.floor_plane) if self.optim_floor else None
@@ -940,7 +963,7 @@ class MotionOptimizer():
             from .fit_kernels import RolloutPost
             from . import _lib as _libmod
             res = self.motion_prior.roll_out(past_in.unsqueeze(1), None, Tm1, z_seq=latent_motion, return_prior=return_prior,
-                                             canonicalize_input=canonicalize_input, return_world=True)
+                                             canonicalize_input=canonicalize_input, return_world=True, **self._feedback_kwargs(B, betas, fit_gender))
             world, prior_out = res if return_prior else (res, None)
             c2p_R = cam2prior[0] if self.optim_floor else None
             c2p_t = cam2prior[1] if self.optim_floor else None
@@ -953,7 +976,7 @@ class MotionOptimizer():
             cam['pose_body'] = out['pose_body']
             return out, cam
         res = self.motion_prior.roll_out(past_in.unsqueeze(1), None, Tm1, z_seq=latent_motion, return_prior=return_prior,
-                                         canonicalize_input=canonicalize_input)
+                                         canonicalize_input=canonicalize_input, **self._feedback_kwargs(B, betas, fit_gender))
         pred, prior_out = res if return_prior else (res, None)
         aa_root = ops.rotation_matrix_to_angle_axis(pred['root_orient'].reshape(-1, 3, 3), _lib_override=lib).reshape(B, Tm1, 3)
         aa_body = ops.rotation_matrix_to_angle_axis(pred['pose_body'].reshape(-1, 3, 3), _lib_override=lib).reshape(B, Tm1, J_BODY * 3)

@@ -30,7 +30,7 @@ extern "C" {
 #define HA_ERR_UNSUPPORTED 3   /* valid request this build cannot serve */
 
 const char* ha_last_error(void);
-/* ABI version of this header (4: + ha_humor_rollout_smpl_joints); bumped on any signature change or addition. */
+/* ABI version of this header (5: + ha_humor_rollout_smpl_joints_fwd / _bwd); bumped on any signature change or addition. */
 int ha_abi_version(void);
 /* Writes the device's gcnArchName (e.g. "gfx950:sramecc+:xnack-") into buf. */
 int ha_device_arch(int device, char* buf, int buflen);
@@ -227,6 +227,26 @@ int ha_humor_rollout_sample(const ha_humor_net* net, int B, int S, const float* 
 int ha_humor_rollout_smpl_joints(const ha_humor_net* net, int B, int S, const float* past_in0, const float* z_seq, const float* eps_seq,
                                  const float* rest_joints, const int32_t* parents, float* world, float* prior_mu, float* prior_var,
                                  float* z_out, float* stash, void* stream);
+
+/* SMPL-joint feedback with gradients (ABI 5; HumorModel(..., smpl_joint_gradients=True)): the pair behind a fit with the HuMoR-Qual
+ * checkpoint (motion_optimizer.py:944-948 rolls out with gender and betas on every stage-3 evaluation, humor_model.py:952 feeds the body
+ * model's joints back without detaching them).  Given z_seq only; arguments as ha_humor_rollout_smpl_joints.
+ * _fwd: ha_humor_rollout_forward on the launch chain (the whole batch, whatever the persistent path's state) with the feedback glue; the
+ * prior network runs once over all stashed states, so that its pre-activations stay for the adjoint.  prior_mu / prior_var: both or NULL.
+ * _bwd: ha_humor_rollout_backward_ex over a stash that _fwd filled, with glue_bwd_fb_kernel in the place of the backward glue: the
+ * gradient arriving on a fed-back joint goes down the kinematic chain into the predicted rotations (through both conversions of the
+ * round trip), the predicted translation and the rest joints; the regressed joints keep the world outputs' gradient.  No launch is added
+ * to a step.  g_world / g_prior_mu / g_prior_var: any may be NULL (zero).  Outputs g_past_in0 [B,339], g_z_seq [B,S,48] (+ g_z_add when
+ * given) and g_rest [B,22,3] = dL/d(rest_joints), zeroed by the call and accumulated over the steps by one owner per element: repeated
+ * calls give identical bits.
+ * A stash remembers which forward filled it: ha_humor_rollout_backward(_ex) on a stash of _fwd returns HA_ERR_INVALID_ARG, and so does
+ * _bwd on a stash of ha_humor_rollout_forward. */
+int ha_humor_rollout_smpl_joints_fwd(const ha_humor_net* net, int B, int S, const float* past_in0, const float* z_seq,
+                                     const float* rest_joints, const int32_t* parents, float* world, float* prior_mu, float* prior_var,
+                                     float* stash, void* stream);
+int ha_humor_rollout_smpl_joints_bwd(const ha_humor_net* net, int B, int S, const float* z_seq, const float* rest_joints,
+                                     const int32_t* parents, const float* g_world, const float* g_prior_mu, const float* g_prior_var,
+                                     float* stash, float* g_past_in0, float* g_z_seq, float* g_rest, const float* g_z_add, void* stream);
 
 /* Backward roll-out: given gradients of the outputs, produce gradients of the inputs.
  *   g_world [B,S,348], g_prior_mu / g_prior_var [B,S,48] (NULL = zero)
