@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, 'csrc', 'libhumor_amd.so')
 
 HA_OK = 0
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int32)
@@ -142,6 +142,9 @@ _SIGS = {
     'ha_lbfgs_scalars': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ha_chamfer_forward': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]),
     'ha_chamfer_backward': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p]),
+    'ha_points_fit_workspace': (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int64)]),
+    'ha_points_fit_forward': (C.c_int, [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 7 + [C.c_void_p]),
+    'ha_points_fit_backward': (C.c_int, [C.c_int] * 3 + [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]),
 }
 
 

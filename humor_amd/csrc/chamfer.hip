@@ -9,7 +9,7 @@
 // on every input, ties included (strict '<' while scanning in index order = the lowest index wins, as in both reference paths).
 // VALU-bound: ~10 instructions per (query, candidate) pair.
 // Backward: gather for the query's own gradient, float atomics for the scattered half (as the reference).
-#include "common.h"
+#include "chamfer_nn.h"
 
 namespace ha {
 
@@ -97,6 +97,12 @@ __global__ void chamfer_grad_kernel(int n, const float* __restrict__ xyz1, int m
   }
 }
 
+int chamfer_nn_launch(int b, int n, const float* xyz1, int m, const float* xyz2, float* dist, int32_t* idx, hipStream_t st) {
+  HA_LAUNCH(chamfer_nn_kernel, dim3(ceil_div(n, 256), b), dim3(256), 3 * CH_CHUNK * sizeof(float), st, n, xyz1, m, xyz2, dist, idx);
+  HA_LAUNCH_CHECK();
+  return HA_OK;
+}
+
 }  // namespace ha
 
 using namespace ha;
@@ -108,12 +114,8 @@ extern "C" int ha_chamfer_forward(int b, int n, const float* xyz1, int m, const 
   HA_REQUIRE(b <= 65535, "ha_chamfer_forward: at most 65535 clouds per call");
   if (b == 0) return HA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = 3 * CH_CHUNK * sizeof(float);
-  HA_LAUNCH(chamfer_nn_kernel, dim3(ceil_div(n, 256), b), dim3(256), lds, st, n, xyz1, m, xyz2, dist1, idx1);
-  HA_LAUNCH_CHECK();
-  HA_LAUNCH(chamfer_nn_kernel, dim3(ceil_div(m, 256), b), dim3(256), lds, st, m, xyz2, n, xyz1, dist2, idx2);
-  HA_LAUNCH_CHECK();
-  return HA_OK;
+  if (int rc = chamfer_nn_launch(b, n, xyz1, m, xyz2, dist1, idx1, st)) return rc;
+  return chamfer_nn_launch(b, m, xyz2, n, xyz1, dist2, idx2, st);
 }
 
 extern "C" int ha_chamfer_backward(int b, int n, const float* xyz1, int m, const float* xyz2, const float* grad_dist1, const int32_t* idx1,

@@ -69,7 +69,7 @@ extern "C" int ha_tune_set(const char* key, int value) {
   return HA_ERR_INVALID_ARG;
 }
 extern "C" const char* ha_last_error(void) { return ha::g_err; }
-extern "C" int ha_abi_version(void) { return 5; }
+extern "C" int ha_abi_version(void) { return 6; }
 extern "C" int ha_device_arch(int device, char* buf, int buflen) {
   HA_REQUIRE(buf && buflen > 0, "ha_device_arch: null buffer");
   hipDeviceProp_t prop;

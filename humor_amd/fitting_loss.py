@@ -103,12 +103,16 @@ class FittingLoss(nn.Module):
 
     def __init__(self, loss_weights, init_motion_prior=None, smpl2op_map=None, ignore_op_joints=None, cam_f=None,
                  cam_cent=None, robust_loss='none', robust_tuning_const=4.6851, joints2d_sigma=100, use_chamfer=False,
-                 fused=True, _lib_override=None):
+                 fused=True, _lib_override=None, fused_points=True):
         super(FittingLoss, self).__init__()
         # fused=True: every term except the init-state GMM is evaluated (value + gradient) by ONE kernel launch
         # (humor_amd/csrc/fitloss.hip, fit_kernels.FusedFit) whenever the predictions live on the GPU; the term-by-term
         # PyTorch evaluation below remains for the cases the kernel does not cover (cross-batch `prev_batch_overlap_res`).
         self.fused = fused
+        # fused_points=True: the points3d term (value + gradient) through the one-way robust op of humor_amd/points_fit.py whenever it
+        # applies (fp32 device tensors, 'none' / 'bisquare', observations without a gradient); the other terms of the objective then
+        # stay on the fused loss kernel.  Otherwise the op chain of points3d_loss and the term-by-term evaluation.
+        self.fused_points = bool(fused_points)
         self.fold_init_prior = True        # stage 3: the init-state GMM term inside the fused loss launches (see _fused_fit)
         self._lib = _lib_override
         self.all_stage_loss_weights = loss_weights
@@ -153,9 +157,19 @@ class FittingLoss(nn.Module):
     # ------------------------------------------------------------------------------------------------
     # fused evaluation (one kernel for all terms and their gradients)
     # ------------------------------------------------------------------------------------------------
-    def _fusable(self, observed_data, ref):
-        if not self.fused or 'prev_batch_overlap_res' in observed_data or 'points3d' in observed_data:
+    def _points_fused(self, points3d_obs, points3d_pred):
+        """The points3d term goes through humor_amd.points_fit (one op) instead of the chamfer / median / weighting op chain."""
+        if not self.fused_points:
             return False
+        from . import points_fit
+        return points_fit.usable(points3d_obs, points3d_pred, self.robust_loss, self._lib)
+
+    def _fusable(self, observed_data, ref, pred_data=None):
+        if not self.fused or 'prev_batch_overlap_res' in observed_data:
+            return False
+        if 'points3d' in observed_data and not (pred_data is not None and 'points3d' in pred_data
+                                                and self._points_fused(observed_data['points3d'], pred_data['points3d'])):
+            return False          # the term's op chain: every term is then evaluated one by one
         if 'joints2d' in observed_data and not self._smpl2op_fusable:
             return False
         if ref.is_cuda:
@@ -312,6 +326,13 @@ class FittingLoss(nn.Module):
                 if use_f:
                     t['floor'] = c(cam['floor_plane'])
         spec['w'] = w
+        if 'points3d' in observed_data and 'points3d' in cam and W['points3d'] > 0.0:
+            # (an addend next to the fused kernel's terms, like the non-folded init-state prior; _fusable has checked that the op applies)
+            cur = self.points3d_loss(observed_data['points3d'], cam['points3d'])
+            extra = W['points3d'] * cur if extra is None else extra + W['points3d'] * cur
+            stats_extra['points3d'] = cur
+            if 'gmm' not in spec and not any(x != 0.0 for x in w):
+                return extra, stats_extra          # the only weighted term: no launch of the fused kernel on an all-zero weight vector
         loss, terms, gmm_total = FK.FusedFit.apply(lib, spec, *[t[n] for n, _ in FK.DIFF_INPUTS])
         stats = {FK.TERM_NAMES[k]: terms[k] for k in range(FK.NT) if w[k] != 0.0}
         if 'gmm' in spec:
@@ -338,7 +359,7 @@ class FittingLoss(nn.Module):
         '''
         W = self.loss_weights
         ref = pred_data.get('joints3d', pred_data.get('verts3d'))
-        if ref is not None and self._fusable(observed_data, ref):
+        if ref is not None and self._fusable(observed_data, ref, pred_data):
             return self._fused_fit('root', observed_data, pred_data, pred_data, 1, halo=halo)
         stats = dict()
         loss = 0.0
@@ -442,7 +463,7 @@ class FittingLoss(nn.Module):
         '''
         W = self.loss_weights
         ref = pred_data.get('joints3d', pred_data.get('verts3d'))
-        if ref is not None and self._fusable(observed_data, ref):
+        if ref is not None and self._fusable(observed_data, ref, pred_data):
             return self._fused_fit('smpl', observed_data, pred_data, pred_data, nsteps, halo=halo)
         fused, self.fused = self.fused, False          # term-by-term path: root_fit must not take the fused branch on its own
         try:
@@ -481,7 +502,7 @@ class FittingLoss(nn.Module):
         '''
         W = self.loss_weights
         ref = cam_pred_data.get('joints3d', cam_pred_data.get('verts3d'))
-        if ref is not None and self._fusable(observed_data, ref):
+        if ref is not None and self._fusable(observed_data, ref, cam_pred_data):
             return self._fused_fit('motion', observed_data, pred_data, cam_pred_data, nsteps, cond_prior=cond_prior,
                                    init_motion_scale=init_motion_scale, halo=halo)
         fused, self.fused = self.fused, False
@@ -574,6 +595,9 @@ class FittingLoss(nn.Module):
         """One-way (observation -> body) chamfer term with robust weighting per sequence (fitting_loss.py:378-396)."""
         if self.chamfer_dist is None:
             raise RuntimeError('FittingLoss(use_chamfer=True) is needed for the points3d term')
+        if self._points_fused(points3d_obs, points3d_pred):
+            from .points_fit import robust_points_loss
+            return robust_points_loss(points3d_obs, points3d_pred, self.robust_loss, self.robust_tuning_const, _lib_override=self._lib)
         B, T, N_obs, _ = points3d_obs.size()
         obs2pred, _ = self.chamfer_dist(points3d_obs.reshape(B * T, -1, 3), points3d_pred.reshape(B * T, -1, 3))
         obs2pred = obs2pred.reshape(B, T * N_obs)

@@ -37,7 +37,7 @@ class MotionOptimizer():
                  robust_tuning_const=4.6851, joint2d_sigma=100, stage3_tune_init_state=True, stage3_tune_init_num_frames=15,
                  stage3_tune_init_freeze_start=30, stage3_tune_init_freeze_end=50, stage3_contact_refine_only=False,
                  use_chamfer=False, im_dim=(1080, 1080), shard=None, verbose=False, use_graphs='auto', fused_loss=True, lbfgs='fused', fused_post=True, fused_pre=True, fused_vposer=True,
-                 rigid_cam_body=True, fused_stage3=True):
+                 rigid_cam_body=True, fused_stage3=True, fused_points=True):
         B, T = batch_size, seq_len
         self.device = device
         self.batch_size, self.seq_len = B, T
@@ -139,7 +139,8 @@ class MotionOptimizer():
             cam_f, cam_c = shard.sl(cam_f), shard.sl(cam_c)
         self.fitting_loss = FittingLoss(loss_weights, self.init_motion_prior, self.smpl2op_map, OP_IGNORE_JOINTS, cam_f, cam_c,
                                         robust_loss_type, robust_tuning_const, joints2d_sigma=joint2d_sigma,
-                                        use_chamfer=self.dense_smpl, fused=fused_loss, _lib_override=self.fit_bm._lib).to(device)
+                                        use_chamfer=self.dense_smpl, fused=fused_loss, _lib_override=self.fit_bm._lib,
+                                        fused_points=fused_points).to(device)
 
     # ------------------------------------------------------------------------------------------------
     # small helpers

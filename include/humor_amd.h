@@ -30,7 +30,7 @@ extern "C" {
 #define HA_ERR_UNSUPPORTED 3   /* valid request this build cannot serve */
 
 const char* ha_last_error(void);
-/* ABI version of this header (5: + ha_humor_rollout_smpl_joints_fwd / _bwd); bumped on any signature change or addition. */
+/* ABI version of this header (5: + ha_humor_rollout_smpl_joints_fwd / _bwd; 6: + ha_points_fit_*); bumped on any signature change or addition. */
 int ha_abi_version(void);
 /* Writes the device's gcnArchName (e.g. "gfx950:sramecc+:xnack-") into buf. */
 int ha_device_arch(int device, char* buf, int buflen);
@@ -479,6 +479,26 @@ int ha_chamfer_forward(int b, int n, const float* xyz1, int m, const float* xyz2
                        int32_t* idx2, void* stream);
 int ha_chamfer_backward(int b, int n, const float* xyz1, int m, const float* xyz2, const float* grad_dist1, const int32_t* idx1,
                         const float* grad_dist2, const int32_t* idx2, float* grad_xyz1, float* grad_xyz2, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The points3d term of a point-cloud fit as one op (FittingLoss.points3d_loss, humor/fitting/fitting_loss.py:378-396, with
+ * apply_robust_weighting / robust_std / bisquare_robust_weights of fitting_utils.py:192-249): ONE-WAY nearest-neighbour search
+ * observation -> vertex (same kernel, arithmetic and tie rule as ha_chamfer_forward), the per-sequence robust scale by radix
+ * selection instead of two sorts (lower median, as torch.median; NaN distances give sigma = NaN), bisquare weights and the value.
+ *   obs [B,T,n_obs,3], pred [B,T,V,3];  robust: 0 none (weights 1; med_d2 / sigma are not written and may be NULL) | 1 bisquare
+ *   d2, idx (int32), weight [B, T*n_obs];  med_d2 [B] = the selected squared distance (median residual = its sqrt);
+ *   sigma [B] = MAD / 0.67449;  loss [B] = 0.5 * sum_i w_i r_i^2, summed in a fixed order.  Every output is fully written.
+ *   `ws`: ha_points_fit_workspace bytes.  No host reads: capturable in a hipGraph.
+ * Backward: g_pred [B,T,V,3] = g_loss[0] (device scalar) * sum_{i: idx_i = v} w_i (pred_v - obs_i), every element written, summed
+ *   in observation order without floating-point atomics: the same bits on every call.  A point that sits ON its vertex contributes
+ *   w * 0 = 0 (the op chain's sqrt backward gives NaN there).  V * 12 B must fit in 150 KB of LDS (V <= 12800), else
+ *   HA_ERR_INVALID_ARG.  `ws` is unused (may be NULL).
+ * ---------------------------------------------------------------------------------------------- */
+int ha_points_fit_workspace(int B, int T, int n_obs, int V, int64_t* bytes);
+int ha_points_fit_forward(int B, int T, int n_obs, const float* obs, int V, const float* pred, int robust, float tune, float* d2,
+                          int32_t* idx, float* weight, float* med_d2, float* sigma, float* loss, void* ws, void* stream);
+int ha_points_fit_backward(int B, int T, int n_obs, const float* obs, int V, const float* pred, const int32_t* idx,
+                           const float* weight, const float* g_loss, float* g_pred, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * L-BFGS direction (the two-loop recursion of torch.optim.LBFGS.step, which the reference drives from
