@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, 'csrc', 'libhumor_amd.so')
 
 HA_OK = 0
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int32)
@@ -23,6 +23,12 @@ class MlpDesc(C.Structure):
 
 
 FIT_NTERMS = 17
+
+
+class GmmArgs(C.Structure):
+    """ha_gmm_args (include/humor_amd.h)."""
+    _fields_ = ([('B', C.c_int), ('K', C.c_int), ('D', C.c_int), ('nseg', C.c_int), ('seg', C.c_void_p * 4), ('seg_width', C.c_int * 4),
+                 ('seg_stride', C.c_int * 4)] + [(n, C.c_void_p) for n in ('means', 'Linv', 'LinvT', 'cst', 'lp', 'gpart', 'nll', 'g_x')])
 
 
 class FitArgs(C.Structure):
@@ -43,7 +49,7 @@ class FitArgs(C.Structure):
                 ('g_prev_tail', C.c_void_p), ('g_prev_betas', C.c_void_p), ('g_prev_floor', C.c_void_p), ('partial', C.c_void_p),
                 ('gmm_nll', C.c_void_p), ('gmm_gx', C.c_void_p), ('gmm_w', C.c_float), ('gmm_D', C.c_int), ('gmm_nseg', C.c_int),
                 ('gmm_g', C.c_void_p * 4), ('gmm_seg_width', C.c_int * 4), ('gmm_g_stride', C.c_int * 4), ('gmm_g_acc', C.c_int * 4),
-                ('gmm_total', C.c_void_p)]
+                ('gmm_total', C.c_void_p), ('gmm', C.POINTER(GmmArgs))]
 
 
 class FitPreArgs(C.Structure):
@@ -63,7 +69,8 @@ class RolloutPostArgs(C.Structure):
         'world', 'trans0', 'root0', 'pose0', 'joints0', 'c2p_R', 'c2p_t',
         'trans', 'root_orient', 'pose_body', 'joints', 'contacts_conf', 'contacts', 'cam_trans', 'cam_root_orient',
         'g_trans', 'g_root_orient', 'g_pose_body', 'g_joints', 'g_contacts_conf', 'g_cam_trans', 'g_cam_root_orient',
-        'g_world', 'g_trans0', 'g_root0', 'g_pose0', 'g_joints0', 'g_c2p_R', 'g_c2p_t', 'partial')]
+        'g_world', 'g_trans0', 'g_root0', 'g_pose0', 'g_joints0', 'g_c2p_R', 'g_c2p_t', 'partial',
+        'sum_src', 'sum_add1', 'sum_add2', 'sum_out')] + [('sum_W', C.c_int)]
 
 
 class RigidImageArgs(C.Structure):
@@ -71,12 +78,6 @@ class RigidImageArgs(C.Structure):
     _fields_ = [('N', C.c_int), ('J', C.c_int), ('V', C.c_int)] + [(n, C.c_void_p) for n in (
         'joints', 'verts', 'root', 'trans', 'root2', 'trans2', 'joints2', 'verts2', 'g_joints2', 'g_verts2',
         'g_joints', 'g_verts', 'g_root', 'g_trans', 'g_root2', 'g_trans2', 'g_joints_add', 'g_verts_add')]
-
-
-class GmmArgs(C.Structure):
-    """ha_gmm_args (include/humor_amd.h)."""
-    _fields_ = ([('B', C.c_int), ('K', C.c_int), ('D', C.c_int), ('nseg', C.c_int), ('seg', C.c_void_p * 4), ('seg_width', C.c_int * 4),
-                 ('seg_stride', C.c_int * 4)] + [(n, C.c_void_p) for n in ('means', 'Linv', 'LinvT', 'cst', 'lp', 'gpart', 'nll', 'g_x')])
 
 
 _SIGS = {

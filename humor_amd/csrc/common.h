@@ -70,6 +70,25 @@ static inline void zero_async(void* p, size_t bytes, hipStream_t st) {
   HA_LAUNCH(zero_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<unsigned*>(p), n);
 }
 
+// out[b][w] = sum_t src[b][t][w] + add1[b][w] + add2[b][w] for one sequence b, by a block's first 256 threads (W <= 64): thread (sl, w) adds up
+// the frames t = sl, sl + 4, ... of column w, the four slices meet in smem [4][64] as (s0 + s1) + (s2 + s3).  Every thread of the block calls it.
+__device__ __forceinline__ void seq_sum_add_block(const float* __restrict__ src, const float* __restrict__ add1, const float* __restrict__ add2,
+                                                  float* __restrict__ out, int b, int T, int W, float* smem) {
+  const int w = threadIdx.x & 63, sl = threadIdx.x >> 6;
+  if (sl < 4) {
+    float acc = 0.f;
+    if (w < W)
+      for (int t = sl; t < T; t += 4) acc += src[((size_t)b * T + t) * W + w];
+    smem[sl * 64 + w] = acc;
+  }
+  __syncthreads();
+  if (sl != 0 || w >= W) return;
+  float acc = (smem[w] + smem[64 + w]) + (smem[128 + w] + smem[192 + w]);
+  if (add1) acc += add1[(size_t)b * W + w];
+  if (add2) acc += add2[(size_t)b * W + w];
+  out[(size_t)b * W + w] = acc;
+}
+
 #define HA_CHECK_HIP(expr)                                                                        \
   do {                                                                                            \
     hipError_t _e = (expr);                                                                       \

@@ -6,10 +6,15 @@
 // input it owns -- temporal terms (smoothness, bone-length change, contact velocity, overlap consistency) in gather form: the
 // wave of frame t recomputes the residuals of the pairs (t-1, t) and (t, t+1) it takes part in, so no gradient is ever
 // accumulated across waves (no atomics: bit-reproducible, which the replicated multi-GPU L-BFGS relies on).  A second
-// single-block launch adds the per-frame partial sums in a fixed order.
-#include "common.h"
+// launch adds the per-frame partial sums in a fixed order.  Given the init-state mixture (ha_fit_args.gmm) the two launches carry its
+// kernels (gmm.hip) as further block roles: blocks of one launch never depend on each other.
+#include "gmm_dev.h"
 
 namespace ha {
+
+// ha_tune_set "loss_merge" (default 1): ha_fit_loss runs the folded init-state prior inside its own two launches and reduces through the LDS
+// (fit_loss_gmm_kernel, fit_finish_kernel), ha_rollout_post_backward's reduction launch does its row-sum task; 0 = one launch per kernel
+int g_loss_merge = 1;
 
 constexpr int NT = HA_FIT_NTERMS;
 constexpr float CONTACT_HEIGHT_THRESH = 0.08f;   // fitting_loss.py:18
@@ -23,10 +28,12 @@ __device__ __forceinline__ float wsum(float v) {
 }
 __device__ __forceinline__ bool visible(float o) { return !(o == INFINITY || o == -INFINITY); }   // get_visible_mask: ~isinf
 
-__global__ __launch_bounds__(64) void fit_loss_kernel(ha_fit_args a) {
-  const int f = blockIdx.x, lane = threadIdx.x;
+constexpr int FIT_WAVE_LDS = 128 + 66;     // floats of LDS per frame: [128] joint -> OpenPose index | [66] bone-length adjoints
+
+// One wavefront evaluates frame f; smem is the wave's own LDS slice (FIT_WAVE_LDS floats), so that wave barriers order its reuse and a
+// block may hold one frame (fit_loss_kernel) or several beside blocks of another role (fit_loss_gmm_kernel).
+__device__ __forceinline__ void fit_loss_frame(const ha_fit_args& a, int f, int lane, float* smem) {
   const int T = a.T, b = f / T, t = f - b * T;
-  extern __shared__ __attribute__((aligned(16))) float smem[];     // [128] joint -> OpenPose index | [66] bone-length adjoints
   int* s_inv = reinterpret_cast<int*>(smem);
   float* s_cu = smem + 128;
   float tv[NT];
@@ -38,10 +45,10 @@ __global__ __launch_bounds__(64) void fit_loss_kernel(ha_fit_args a) {
   if (a.cam_jtr) {
     const int nj = a.nj;
     for (int j = lane; j < nj; j += 64) s_inv[j] = -1;
-    __syncthreads();
+    wave_sync();
     const bool use2d = a.obs_j2d != nullptr && w[HA_FIT_J2D] != 0.f;
     if (use2d && lane < 25) s_inv[a.smpl2op[lane]] = lane;
-    __syncthreads();
+    wave_sync();
     const float* P = a.cam_jtr + (size_t)f * nj * 3;
     for (int j = lane; j < nj; j += 64) {
       const float p[3] = {P[j * 3], P[j * 3 + 1], P[j * 3 + 2]};
@@ -233,9 +240,9 @@ __global__ __launch_bounds__(64) void fit_loss_kernel(ha_fit_args a) {
       }
     }
     // bone-length adjoint: joint j receives +cu[j] as the child end of its bone and -cu[child] from every bone it parents
-    __syncthreads();
+    wave_sync();
     if (j < 22) { s_cu[j * 3] = cu[0]; s_cu[j * 3 + 1] = cu[1]; s_cu[j * 3 + 2] = cu[2]; }
-    __syncthreads();
+    wave_sync();
     if (j < 22) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) gr[c] += cu[c];
@@ -350,6 +357,21 @@ __global__ __launch_bounds__(64) void fit_loss_kernel(ha_fit_args a) {
   }
 }
 
+__global__ __launch_bounds__(64) void fit_loss_kernel(ha_fit_args a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  fit_loss_frame(a, blockIdx.x, threadIdx.x, smem);
+}
+
+// The per-frame waves and the (sequence, component) blocks of the init-state mixture in one grid: blocks < n_loss hold GMM_WAVES frames
+// (one wave each, no block barrier), the others are gmm_comp_kernel's.  Neither role reads what the other writes: `a` arrives with
+// gmm_gx == NULL, the mixture's gradient is applied by fit_finish_kernel.
+__global__ __launch_bounds__(GMM_WAVES * 64) void fit_loss_gmm_kernel(ha_fit_args a, ha_gmm_args g, int n_loss) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  if ((int)blockIdx.x >= n_loss) { gmm_comp_block(g, blockIdx.x - n_loss, smem); return; }
+  const int wave = threadIdx.x >> 6, f = blockIdx.x * GMM_WAVES + wave;
+  if (f < a.B * a.T) fit_loss_frame(a, f, threadIdx.x & 63, smem + wave * FIT_WAVE_LDS);
+}
+
 // terms[k] = sum over frames (fixed order), loss = sum_k weff_k terms[k].  One wave per term (lane-strided partial sums, then
 // an xor-shuffle tree: a fixed association, so the value is bit-reproducible), no block barriers in the summation.
 __global__ __launch_bounds__(1024) void fit_reduce_kernel(ha_fit_args a) {
@@ -392,12 +414,137 @@ __global__ __launch_bounds__(1024) void fit_reduce_kernel(ha_fit_args a) {
   }
 }
 
+constexpr int RED_CH = 256;                              // frames per staged chunk = one trip of fit_reduce_kernel's unrolled loop
+constexpr int RED_LD = (RED_CH * NT + 1023) / 1024;      // loads per thread and chunk
+constexpr int RED_G = 8;                                 // chunks whose loads are issued together (even: two LDS buffers alternate)
+
+// Block 0: fit_reduce_kernel's sums in the same association, but the [frame][NT] rows come through the LDS in chunks of RED_CH frames --
+// whole lines per load instruction instead of 64 lines for 64 floats, the loads of RED_G chunks (2048 frames) in flight together.
+// Blocks 1 .. B (only when ha_fit_loss runs the mixture itself): gmm_mix_kernel for sequence blockIdx.x - 1, then the mixture's gradient
+// goes where fit_loss_frame puts it when it finds gmm_gx: fmaf(gmm_w, gx, stored) on frame 0 of g_pri_joints, gmm_w * gx to the other
+// segments' slots.  Block 0 does not wait for them: it recomputes every nll_b from lp with the function they use.
+__global__ __launch_bounds__(1024) void fit_finish_kernel(ha_fit_args a, ha_gmm_args g) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nmix = gridDim.x - 1;
+  if (blockIdx.x > 0) {
+    float* wk = smem;                                    // [64] mixture weights
+    const int b = blockIdx.x - 1;
+    if (tid < 64) {
+      const float nll = gmm_wave_nll(g, b, tid, wk[tid]);
+      if (tid == 0) g.nll[b] = nll;
+    }
+    __syncthreads();
+    for (int i = tid; i < g.D; i += 1024) {
+      const float gx = gmm_mix_grad(g, b, i, wk);
+      g.g_x[(size_t)b * g.D + i] = gx;
+      int o = i, sgm = 0;
+      while (sgm + 1 < a.gmm_nseg && o >= a.gmm_seg_width[sgm]) { o -= a.gmm_seg_width[sgm]; ++sgm; }
+      float* dst = a.gmm_g[sgm];
+      if (sgm == 0) {                                    // the 22 joints of frame 0, on top of what the loss kernel stored
+        if (dst && a.g_pri_joints) {
+          float* p = a.g_pri_joints + (size_t)b * a.T * a.pri_nj * 3 + o;
+          *p = fmaf(a.gmm_w, gx, *p);
+        }
+      } else if (dst) {
+        dst[(size_t)b * a.gmm_g_stride[sgm] + o] = a.gmm_w * gx;
+      }
+    }
+    return;
+  }
+  float* sterm = smem + 2 * RED_CH * NT;                 // [NT] term values | init-state prior total; in front of it two chunks [RED_CH][NT]
+  float* snll = sterm + NT + 1;                          // [B] nll_b (nmix > 0)
+  const int F = a.B * a.T;
+  const size_t last = (size_t)F * NT - 1;
+  // the wave's first row of lp ahead of the partial sums' loads (unconditional, clamped: see below)
+  const int kl = nmix > 0 && lane < g.K ? lane : 0;
+  float lp_next = nmix > 0 ? g.lp[(size_t)(wave < a.B ? wave : 0) * g.K + kl] : 0.f;
+  float s[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};      // wave w: terms w and w + 16
+  for (int gbase = 0; gbase < F; gbase += RED_G * RED_CH) {
+    // every load of the group's chunks at once: one round trip to memory per RED_G * RED_CH frames
+    float r[RED_G][RED_LD];
+#pragma unroll
+    for (int c = 0; c < RED_G; ++c) {
+      const int base = gbase + c * RED_CH;
+      // (unconditional loads, the index clamped to the last partial sum: a load under a condition is waited for on its own; the chunk's
+      // write pass drops what lies beyond it)
+#pragma unroll
+      for (int u = 0; u < RED_LD; ++u) {
+        const size_t i = (size_t)base * NT + tid + 1024 * u;
+        r[c][u] = a.partial[i < last ? i : last];
+      }
+    }
+    if (gbase == 0 && nmix > 0)                          // wave w: nll of the sequences w, w + 16, ... (the next one's row is on its way)
+      for (int b = wave; b < a.B; b += 16) {
+        const float v = lane < g.K ? lp_next : -INFINITY;
+        if (b + 16 < a.B) lp_next = g.lp[(size_t)(b + 16) * g.K + kl];
+        float wgt;
+        const float nll = gmm_wave_nll_of(v, g.K, lane, wgt);
+        if (lane == 0) snll[b] = nll;
+      }
+    // chunk c goes through buffer c & 1: its last readers (chunk c - 2) are behind the barrier of chunk c - 1, RED_G is even
+#pragma unroll
+    for (int c = 0; c < RED_G; ++c) {
+      const int base = gbase + c * RED_CH;
+      if (base >= F) break;
+      const int n = (F - base < RED_CH ? F - base : RED_CH) * NT;
+      float* chunk = smem + (c & 1) * RED_CH * NT;
+#pragma unroll
+      for (int u = 0; u < RED_LD; ++u) { const int i = tid + 1024 * u; if (i < n) chunk[i] = r[c][u]; }
+      __syncthreads();
+#pragma unroll
+      for (int ki = 0; ki < 2; ++ki) {
+        const int k = wave + 16 * ki, f = base + lane;
+        if (k >= NT) continue;
+        if (f + 192 < F) {
+          s[ki][0] += chunk[lane * NT + k];
+          s[ki][1] += chunk[(lane + 64) * NT + k];
+          s[ki][2] += chunk[(lane + 128) * NT + k];
+          s[ki][3] += chunk[(lane + 192) * NT + k];
+        } else {                                         // the lane's last frames: all into s0, as fit_reduce_kernel's remainder loop
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (f + 64 * j < F) s[ki][0] += chunk[(lane + 64 * j) * NT + k];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int ki = 0; ki < 2; ++ki) {
+    const int k = wave + 16 * ki;
+    if (k >= NT) continue;
+    const float v = wsum((s[ki][0] + s[ki][1]) + (s[ki][2] + s[ki][3]));
+    if (lane == 0) sterm[k] = v;
+  }
+  const bool fold = nmix > 0 || a.gmm_nll != nullptr;
+  if (fold && wave == 15) {
+    float v = 0.f;
+    for (int b = lane; b < a.B; b += 64) v += nmix > 0 ? snll[b] : a.gmm_nll[b];
+    v = wsum(v);
+    if (lane == 0) sterm[NT] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float loss = 0.f;
+    for (int k = 0; k < NT; ++k) {
+      a.terms[k] = sterm[k];
+      const float scale = (k == HA_FIT_SHAPE_PRIOR || k == HA_FIT_FLOOR_REG) ? a.nsteps : 1.f;
+      loss += a.w[k] * scale * sterm[k];
+    }
+    if (fold) {
+      const float tot = sterm[NT];
+      if (a.gmm_total) a.gmm_total[0] = tot;
+      loss += a.gmm_w * tot;
+    }
+    a.loss[0] = loss;
+  }
+}
+
 }  // namespace ha
 
 extern "C" int ha_fit_loss(const ha_fit_args* args, void* stream) {
   using namespace ha;
   HA_REQUIRE(args, "ha_fit_loss: null argument");
-  const ha_fit_args& a = *args;
+  ha_fit_args a = *args;
   HA_REQUIRE(a.B >= 1 && a.T >= 1, "ha_fit_loss: B and T must be >= 1");
   HA_REQUIRE(a.partial && a.terms && a.loss, "ha_fit_loss: partial / terms / loss buffers are required");
   HA_REQUIRE(!a.cam_jtr || (a.nj >= 22 && a.nj <= 128), "ha_fit_loss: nj must be in [22, 128]");
@@ -406,11 +553,41 @@ extern "C" int ha_fit_loss(const ha_fit_args* args, void* stream) {
   HA_REQUIRE(!a.latent_motion || (a.S >= 1 && a.S <= a.T && a.dz >= 1), "ha_fit_loss: latent steps S must be in [1, T]");
   HA_REQUIRE((a.prior_mu == nullptr) == (a.prior_var == nullptr), "ha_fit_loss: prior_mu and prior_var go together");
   HA_REQUIRE(!a.prev_tail || (a.cam_verts && a.overlap), "ha_fit_loss: a halo tail needs cam_verts and the overlap table");
+  const ha_gmm_args* gm = a.gmm;
+  if (gm) {
+    const int rc = gmm_check_args(*gm, "ha_fit_loss (gmm)");
+    if (rc != HA_OK) return rc;
+    HA_REQUIRE(gm->B == a.B && gm->D == a.gmm_D && gm->nseg == a.gmm_nseg, "ha_fit_loss: gmm's B, D, nseg differ from B, gmm_D, gmm_nseg");
+    for (int sg = 0; sg < gm->nseg; ++sg)
+      HA_REQUIRE(gm->seg_width[sg] == a.gmm_seg_width[sg], "ha_fit_loss: gmm_seg_width[%d] differs from the mixture's segment", sg);
+    a.gmm_nll = gm->nll;
+    a.gmm_gx = gm->g_x;
+  }
   HA_REQUIRE(!a.gmm_gx || (a.gmm_nll && a.gmm_D >= 1 && a.gmm_nseg >= 1 && a.gmm_nseg <= 4), "ha_fit_loss: the folded init-state prior needs gmm_nll, gmm_D and 1..4 segments");
   hipStream_t st = (hipStream_t)stream;
-  HA_LAUNCH(fit_loss_kernel, dim3(a.B * a.T), dim3(64), (128 + 66) * sizeof(float), st, a);
+  const size_t red_lds = ((size_t)2 * RED_CH * NT + NT + 1 + (gm ? a.B : 0)) * sizeof(float);
+  if (gm && g_loss_merge) {
+    HA_REQUIRE(a.B <= 4096, "ha_fit_loss: the folded init-state prior serves at most 4096 sequences");
+    HA_REQUIRE(!a.gmm_g[0] || (a.pri_joints && a.gmm_seg_width[0] == 66), "ha_fit_loss: segment 0 of the folded prior is the 22 joints of pri_joints");
+    ha_fit_args a1 = a;
+    a1.gmm_gx = nullptr;                       // the frame-0 waves leave the mixture's gradient to fit_finish_kernel
+    const int n_loss = ceil_div(a.B * a.T, GMM_WAVES);
+    const size_t lds_loss = (size_t)GMM_WAVES * FIT_WAVE_LDS, lds_gmm = gmm_comp_lds_floats(gm->D);
+    HA_LAUNCH(fit_loss_gmm_kernel, dim3(n_loss + gm->B * gm->K), dim3(GMM_WAVES * 64), (lds_loss > lds_gmm ? lds_loss : lds_gmm) * sizeof(float), st,
+              a1, *gm, n_loss);
+    HA_LAUNCH_CHECK();
+    HA_LAUNCH(fit_finish_kernel, dim3(1 + a.B), dim3(1024), red_lds, st, a, *gm);
+    HA_LAUNCH_CHECK();
+    return HA_OK;
+  }
+  if (gm) {
+    const int rc = ha_gmm_nll(gm, stream);
+    if (rc != HA_OK) return rc;
+  }
+  HA_LAUNCH(fit_loss_kernel, dim3(a.B * a.T), dim3(64), FIT_WAVE_LDS * sizeof(float), st, a);
   HA_LAUNCH_CHECK();
-  HA_LAUNCH(fit_reduce_kernel, dim3(1), dim3(1024), (NT + 1) * sizeof(float), st, a);
+  if (g_loss_merge) HA_LAUNCH(fit_finish_kernel, dim3(1), dim3(1024), red_lds, st, a, ha_gmm_args{});
+  else HA_LAUNCH(fit_reduce_kernel, dim3(1), dim3(1024), (NT + 1) * sizeof(float), st, a);
   HA_LAUNCH_CHECK();
   return HA_OK;
 }

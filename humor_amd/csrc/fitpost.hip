@@ -197,6 +197,43 @@ __global__ __launch_bounds__(64) void rollout_post_reduce_kernel(ha_rollout_post
   else a.g_trans0[(size_t)b * 3 + (i - 12)] = s;
 }
 
+constexpr int POST_CH = 64;               // frames per staged chunk of rollout_post_sums_kernel
+constexpr int POST_LD = (POST_CH * NPART + 255) / 256;      // loads per thread and chunk
+
+// rollout_post_reduce_kernel and the optional row-sum task (ha_seq_sum_add's work) in one launch of 256-thread blocks.
+// Blocks < B: the sequence's T x 15 partials are contiguous -- all threads fetch a chunk of POST_CH frames at once (independent, coalesced
+// loads instead of one dependent load per frame and lane), lanes < 15 then add in ascending t as rollout_post_reduce_kernel does.
+// Blocks >= B: seq_sum_add_block for sequence blockIdx.x - B.
+__global__ __launch_bounds__(256) void rollout_post_sums_kernel(ha_rollout_post_args a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];     // [POST_CH][15] | [4][64]
+  const int T = a.S + 1, i = threadIdx.x;
+  if ((int)blockIdx.x >= a.B) {
+    seq_sum_add_block(a.sum_src, a.sum_add1, a.sum_add2, a.sum_out, blockIdx.x - a.B, T, a.sum_W, smem);
+    return;
+  }
+  const int b = blockIdx.x;
+  const float* P = a.partial + (size_t)b * T * NPART;
+  float s = 0.f;
+  for (int t0 = 0; t0 < T; t0 += POST_CH) {
+    const int nt = T - t0 < POST_CH ? T - t0 : POST_CH;
+    float r[POST_LD];                 // (unconditional loads, index clamped to the chunk: a load under a condition is waited for on its own)
+#pragma unroll
+    for (int u = 0; u < POST_LD; ++u) { const int e = i + 256 * u; r[u] = P[(size_t)t0 * NPART + (e < nt * NPART ? e : nt * NPART - 1)]; }
+#pragma unroll
+    for (int u = 0; u < POST_LD; ++u) { const int e = i + 256 * u; if (e < nt * NPART) smem[e] = r[u]; }
+    __syncthreads();
+    if (i < NPART)
+      for (int t = 0; t < nt; ++t) s += smem[t * NPART + i];
+    __syncthreads();
+  }
+  if (i >= NPART) return;
+  if (i < 9) { if (a.g_c2p_R) a.g_c2p_R[(size_t)b * 9 + i] = s; }
+  else if (i < 12) { if (a.g_c2p_t) a.g_c2p_t[(size_t)b * 3 + (i - 9)] = s; }
+  else a.g_trans0[(size_t)b * 3 + (i - 12)] = s;
+}
+
+extern int g_loss_merge;      // fitloss.hip
+
 }  // namespace ha
 
 using namespace ha;
@@ -221,10 +258,16 @@ extern "C" int ha_rollout_post_backward(const ha_rollout_post_args* args, void* 
   HA_REQUIRE(a.world && a.trans0 && a.root_orient && a.contacts_conf, "ha_rollout_post_backward: forward tensors missing");
   HA_REQUIRE(a.g_world && a.g_trans0 && a.g_root0 && a.g_pose0 && a.g_joints0 && a.partial, "ha_rollout_post_backward: null output");
   HA_REQUIRE(!a.c2p_R || (a.g_c2p_R && a.g_c2p_t), "ha_rollout_post_backward: cam2prior gradient outputs missing");
+  HA_REQUIRE(!a.sum_src || (a.sum_out && a.sum_W >= 1 && a.sum_W <= 64), "ha_rollout_post_backward: the row-sum task needs sum_out and 1 <= sum_W <= 64");
   hipStream_t st = (hipStream_t)stream;
+  if (a.sum_src && !g_loss_merge) {
+    const int rc = ha_seq_sum_add(a.B, a.S + 1, a.sum_W, a.sum_src, a.sum_add1, a.sum_add2, a.sum_out, stream);
+    if (rc != HA_OK) return rc;
+  }
   HA_LAUNCH(rollout_post_bwd_kernel, dim3(a.B * (a.S + 1)), dim3(64), 0, st, a);
   HA_LAUNCH_CHECK();
-  HA_LAUNCH(rollout_post_reduce_kernel, dim3(a.B), dim3(64), 0, st, a);
+  if (g_loss_merge) HA_LAUNCH(rollout_post_sums_kernel, dim3(a.B * (a.sum_src ? 2 : 1)), dim3(256), POST_CH * NPART * sizeof(float), st, a);
+  else HA_LAUNCH(rollout_post_reduce_kernel, dim3(a.B), dim3(64), 0, st, a);
   HA_LAUNCH_CHECK();
   return HA_OK;
 }

@@ -48,6 +48,7 @@ int g_dense_gA_sparse = 2;   // ha_tune_set("dense_gA_sparse"): dL/dA of the den
 int g_dense_bwd_waves = 0;   // ha_tune_set("dense_bwd_waves"): wave-count target of the dense backward's K split (0 = default)
 extern int g_layer_finish, g_gemm_rm, g_rollout_groups, g_gemm_ks, g_gemm_fold, g_rollout_persist, g_rollout_persist_bwd, g_rollout_persist_inject, g_rollout_pipe, g_rollout_pipe_bwd;   // rollout.hip
 extern unsigned g_cu_poison;   // debug.hip
+extern int g_loss_merge;       // fitloss.hip
 }
 extern "C" int ha_tune_set(const char* key, int value) {
   HA_REQUIRE(key, "ha_tune_set: null key");
@@ -63,13 +64,14 @@ extern "C" int ha_tune_set(const char* key, int value) {
   if (strcmp(key, "rollout_persist_bwd") == 0) { ha::g_rollout_persist_bwd = value; return HA_OK; }
   if (strcmp(key, "rollout_pipe") == 0) { ha::g_rollout_pipe = value; return HA_OK; }
   if (strcmp(key, "rollout_pipe_bwd") == 0) { ha::g_rollout_pipe_bwd = value; return HA_OK; }
+  if (strcmp(key, "loss_merge") == 0) { ha::g_loss_merge = value; return HA_OK; }
   if (strcmp(key, "rollout_persist_inject") == 0) { ha::g_rollout_persist_inject = value; return HA_OK; }
   if (strcmp(key, "cu_poison") == 0) { ha::g_cu_poison = (unsigned)value; return HA_OK; }
   ha::set_error("ha_tune_set: unknown key '%s'", key);
   return HA_ERR_INVALID_ARG;
 }
 extern "C" const char* ha_last_error(void) { return ha::g_err; }
-extern "C" int ha_abi_version(void) { return 6; }
+extern "C" int ha_abi_version(void) { return 7; }
 extern "C" int ha_device_arch(int device, char* buf, int buflen) {
   HA_REQUIRE(buf && buflen > 0, "ha_device_arch: null buffer");
   hipDeviceProp_t prop;
@@ -2105,17 +2107,7 @@ namespace ha {
 __global__ __launch_bounds__(256) void seq_sum_add_kernel(const float* __restrict__ src, const float* __restrict__ add1,
                                                           const float* __restrict__ add2, float* __restrict__ out, int T, int W) {
   extern __shared__ __attribute__((aligned(16))) float smem[];     // [4][64] partial sums of the four frame slices
-  const int b = blockIdx.x, w = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  float acc = 0.f;
-  if (w < W)
-    for (int t = sl; t < T; t += 4) acc += src[((size_t)b * T + t) * W + w];
-  smem[sl * 64 + w] = acc;
-  __syncthreads();
-  if (sl != 0 || w >= W) return;
-  acc = (smem[w] + smem[64 + w]) + (smem[128 + w] + smem[192 + w]);
-  if (add1) acc += add1[(size_t)b * W + w];
-  if (add2) acc += add2[(size_t)b * W + w];
-  out[(size_t)b * W + w] = acc;
+  seq_sum_add_block(src, add1, add2, out, blockIdx.x, T, W, smem);
 }
 }  // namespace ha
 

@@ -23,7 +23,7 @@ DIFF_INPUTS = [('cam_jtr', 'g_cam_jtr'), ('cam_verts', 'g_cam_verts'), ('pri_joi
                ('contacts_conf', 'g_contacts_conf'), ('latent_pose', 'g_latent_pose'), ('betas', 'g_betas'),
                ('latent_motion', 'g_latent_motion'), ('prior_mu', 'g_prior_mu'), ('prior_var', 'g_prior_var'), ('floor', 'g_floor'),
                ('prev_tail', 'g_prev_tail'), ('prev_betas', 'g_prev_betas'), ('prev_floor', 'g_prev_floor'),
-               # inputs of the folded init-state prior only (spec['gmm']): their gradients come from ha_gmm_nll through ha_fit_loss
+               # inputs of the folded init-state prior only (spec['gmm']): their gradients come from the mixture blocks of ha_fit_loss
                ('joints_vel', None), ('trans_vel', None), ('root_orient_vel', None)]
 GMM_INPUTS = ('joints_vel', 'trans_vel', 'root_orient_vel')
 CONST_INPUTS = ['obs_j2d', 'smpl2op', 'op_mask', 'cam_f', 'cam_c', 'obs_j3d', 'obs_v3d', 'obs_floor', 'overlap']
@@ -96,8 +96,8 @@ class FusedFit(torch.autograd.Function):
         a.terms, a.loss, a.partial = base + ng * esz, base + (ng + NT) * esz, base + (ng + NT + 2) * esz
         gmm = spec.get('gmm')
         if gmm is not None:
-            # init-state prior (FittingLoss.init_motion_prior_loss): ha_gmm_nll on [frame 0 of the prior-frame joints | joints_vel |
-            # trans_vel | root_orient_vel], its value and gradient folded into the objective by ha_fit_loss's reduction kernel
+            # init-state prior (FittingLoss.init_motion_prior_loss): the mixture on [frame 0 of the prior-frame joints | joints_vel |
+            # trans_vel | root_orient_vel], evaluated by ha_fit_loss inside its own two launches and folded into the objective there
             pj = named['pri_joints']
             segs = [(pj, 66, a.T * a.pri_nj * 3)] + [(named[k], named[k][0].numel(), named[k][0].numel()) for k in GMM_INPUTS]
             g = gmm['gmm']
@@ -110,7 +110,7 @@ class FusedFit(torch.autograd.Function):
             tb = g.device_tables(dev)
             for k, v in dict(means=tb['means'], Linv=tb['Linv'], LinvT=tb['LinvT'], cst=tb['const'], lp=lp, gpart=gpart, nll=nll, g_x=g_x).items():
                 setattr(ga, k, v.data_ptr())
-            lib.call('ha_gmm_nll', C.byref(ga), _lib.stream_ptr(ref))
+            a.gmm = C.pointer(ga)
             keep += [lp, gpart, nll, g_x]
             a.gmm_nll, a.gmm_gx, a.gmm_w, a.gmm_D, a.gmm_nseg = nll.data_ptr(), g_x.data_ptr(), float(gmm['w']), D, len(segs)
             a.gmm_g[0], a.gmm_seg_width[0], a.gmm_g_stride[0], a.gmm_g_acc[0] = goff['pri_joints'], 66, a.T * a.pri_nj * 3, 1

@@ -218,8 +218,7 @@ class Stage3Body(torch.autograd.Function):
                  sm['n_sel'], _p(g_jtr), 0, 0, _p(g_verts), _p(add_root), _p(g_pose), None, _p(add_transl),
                  _p(g_ro), _p(g_pb), _p(g_bf), _p(g_tl), st)
         g_betas = _new(dev, B, NB)
-        lib.call('ha_seq_sum_add', B, T, NB, _p(g_bf), _p(g_betas_t), None, _p(g_betas), st)
-        # adjoint of the post-processing
+        # adjoint of the post-processing; the row sum of the per-frame shape gradients (+ the loss's own) rides in its reduction launch
         gw, gt0, gr0, gp0, gj0 = _new(dev, B, S, 348), _new(dev, B, 3), _new(dev, B, 3), _new(dev, B, 63), _new(dev, B, 22, 3)
         gR, gt = (_new(dev, B, 3, 3), _new(dev, B, 3)) if ctx.cam else (None, None)
         partial = _new(dev, N, 15)
@@ -228,9 +227,10 @@ class Stage3Body(torch.autograd.Function):
         fields = dict(world=world, trans0=trans0, root0=root0, c2p_R=c2p_R, c2p_t=c2p_t, root_orient=root_orient, contacts_conf=conf,
                       g_trans=g_tl, g_root_orient=g_ro, g_pose_body=g_pb, g_joints=g_ro_joints, g_contacts_conf=g_conf,
                       g_cam_trans=g_t2, g_cam_root_orient=g_r2, g_world=gw, g_trans0=gt0, g_root0=gr0, g_pose0=gp0, g_joints0=gj0,
-                      g_c2p_R=gR, g_c2p_t=gt, partial=partial)
+                      g_c2p_R=gR, g_c2p_t=gt, partial=partial, sum_src=g_bf, sum_add1=g_betas_t, sum_out=g_betas)
         for k, v in fields.items():
             if v is not None:
                 setattr(a, k, v.data_ptr())
+        a.sum_W = NB
         lib.call('ha_rollout_post_backward', C.byref(a), st)
         return None, gw, gt0, gr0, gp0, gj0, gR, gt, g_betas

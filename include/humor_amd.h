@@ -30,11 +30,11 @@ extern "C" {
 #define HA_ERR_UNSUPPORTED 3   /* valid request this build cannot serve */
 
 const char* ha_last_error(void);
-/* ABI version of this header (5: + ha_humor_rollout_smpl_joints_fwd / _bwd; 6: + ha_points_fit_*); bumped on any signature change or addition. */
+/* ABI version of this header (5: + ha_humor_rollout_smpl_joints_fwd / _bwd; 6: + ha_points_fit_*; 7: ha_fit_args.gmm, the row-sum task of ha_rollout_post_args, "loss_merge"); bumped on any signature change or addition. */
 int ha_abi_version(void);
 /* Writes the device's gcnArchName (e.g. "gfx950:sramecc+:xnack-") into buf. */
 int ha_device_arch(int device, char* buf, int buflen);
-/* Development knobs for kernel launch variants (A/B measurements), process-wide: "skin_variant" (-1 = auto), "layer_finish" (0 never / 1 auto / 2 always use the GroupNorm finishing pass), "gemm_rm" (row tiles per wave of the batched prior GEMM: 0 by size / 1 / 2), "gemm_ks" (short-chain forms of the small batched GEMMs: 0 = plain form everywhere, 2 = by the launch policy, 3 = force the deepest K split), "gemm_fold" (1 = the layout-only passes around the batched GEMMs -- prior_mu / prior_var of a roll-out, y / g_x / a narrow x of ha_mlp_* -- are done by the GEMM itself, 0 = separate launches), "rollout_persist" / "rollout_persist_bwd" (0 = launch chain; 1 = persistent kernels, 3 = with write-through publishes), "rollout_pipe" / "rollout_pipe_bwd" (batches of more than 32 sequences: 1 = the layer-parallel pipelined persistent kernels, 0 = launch chain; set the adjoint knobs before the forward call), "rollout_persist_inject" (test hook: 1 = the next persistent forwards drop one CU of team 0, so that the failure path -- NaN results, error word -- can be exercised), "cu_poison" (test hook: != 0 = every kernel launch of this library is preceded by a kernel that fills the LDS and the vector registers of every CU with a bit pattern -- 1 = a quiet NaN, else the value itself -- so that a read of state the kernel did not write shows on every box). */
+/* Development knobs for kernel launch variants (A/B measurements), process-wide: "skin_variant" (-1 = auto), "layer_finish" (0 never / 1 auto / 2 always use the GroupNorm finishing pass), "gemm_rm" (row tiles per wave of the batched prior GEMM: 0 by size / 1 / 2), "gemm_ks" (short-chain forms of the small batched GEMMs: 0 = plain form everywhere, 2 = by the launch policy, 3 = force the deepest K split), "gemm_fold" (1 = the layout-only passes around the batched GEMMs -- prior_mu / prior_var of a roll-out, y / g_x / a narrow x of ha_mlp_* -- are done by the GEMM itself, 0 = separate launches), "rollout_persist" / "rollout_persist_bwd" (0 = launch chain; 1 = persistent kernels, 3 = with write-through publishes), "rollout_pipe" / "rollout_pipe_bwd" (batches of more than 32 sequences: 1 = the layer-parallel pipelined persistent kernels, 0 = launch chain; set the adjoint knobs before the forward call), "loss_merge" (1 = ha_fit_loss runs the folded init-state prior inside its own two launches, its reduction reads the per-frame partial sums through the LDS, and ha_rollout_post_backward's reduction launch also does its row-sum task; 0 = one launch per kernel, as up to ABI 6), "rollout_persist_inject" (test hook: 1 = the next persistent forwards drop one CU of team 0, so that the failure path -- NaN results, error word -- can be exercised), "cu_poison" (test hook: != 0 = every kernel launch of this library is preceded by a kernel that fills the LDS and the vector registers of every CU with a bit pattern -- 1 = a quiet NaN, else the value itself -- so that a read of state the kernel did not write shows on every box). */
 int ha_tune_set(const char* key, int value);
 /* Test support: fills the LDS and every VGPR / AGPR of all CUs with `pattern` (0 = quiet NaN) on `stream`; with `surviving_words` non-null it then
  * synchronises the stream and counts the LDS words (of 256 x 40960) a following kernel still finds holding the pattern -- 0 means this box clears
@@ -369,6 +369,11 @@ typedef struct ha_fit_args {
   const float* gmm_nll; const float* gmm_gx; float gmm_w; int gmm_D; int gmm_nseg;
   float* gmm_g[4]; int gmm_seg_width[4]; int gmm_g_stride[4]; int gmm_g_acc[4];
   float* gmm_total;
+  /* optional (ABI 7): the mixture itself.  Non-NULL = ha_fit_loss evaluates the init-state prior too (the caller does not run ha_gmm_nll), inside
+   * its own two launches: the (sequence, component) blocks share the grid of the per-frame blocks, the mixing blocks that of the reduction
+   * (which adds up nll from lp itself), and the mixing blocks hand gmm_w * g_x out to gmm_g[] behind the loss kernel's stores.  gmm_nll /
+   * gmm_gx are then taken from gmm->nll / gmm->g_x (both are still written); gmm_w, gmm_D, gmm_nseg, gmm_g*, gmm_total as above. */
+  const struct ha_gmm_args* gmm;
 } ha_fit_args;
 
 int ha_fit_loss(const ha_fit_args* args, void* stream);
@@ -423,6 +428,9 @@ typedef struct ha_rollout_post_args {
   /* ... and of the inputs */
   float* g_world; float* g_trans0; float* g_root0; float* g_pose0; float* g_joints0; float* g_c2p_R; float* g_c2p_t;
   float* partial;                                   /* workspace [B*T, 15] */
+  /* optional (ABI 7), backward only: a row-sum task that rides in the reduction launch -- sum_out [B,sum_W] = sum_t sum_src [B,T,sum_W] +
+   * sum_add1 [B,sum_W] + sum_add2 [B,sum_W], exactly ha_seq_sum_add(B, T, sum_W, ...) (addends may be NULL; sum_src NULL = no task) */
+  const float* sum_src; const float* sum_add1; const float* sum_add2; float* sum_out; int sum_W;
 } ha_rollout_post_args;
 int ha_rollout_post_forward(const ha_rollout_post_args* args, void* stream);
 int ha_rollout_post_backward(const ha_rollout_post_args* args, void* stream);
