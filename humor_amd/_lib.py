@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, 'csrc', 'libhumor_amd.so')
 
 HA_OK = 0
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int32)
@@ -60,7 +60,10 @@ class FitPreArgs(C.Structure):
         'g_past_in', 'g_trans_p', 'g_root_p', 'g_joints_p', 'g_c2p_R', 'g_c2p_t', 'g_root_height',
         'g_floor', 'g_trans0', 'g_root0', 'g_pose0', 'g_jcam', 'g_trans_vel', 'g_joints_vel', 'g_root_orient_vel')]
                 + [('jcam_stride', C.c_int)] + [(n, C.c_void_p) for n in (
-                    'add_floor', 'add_pose0', 'add_trans_vel', 'add_joints_vel', 'add_root_orient_vel')])
+                    'add_floor', 'add_pose0', 'add_trans_vel', 'add_joints_vel', 'add_root_orient_vel')]
+                # turn-around riders (ABI 8)
+                + [('clr', C.c_void_p), ('clr_words', C.c_int64), ('dz_part', C.c_void_p), ('dz_g_z', C.c_void_p), ('dz_g_z_add', C.c_void_p),
+                   ('dz_B', C.c_int), ('dz_S', C.c_int), ('dz_slots', C.c_int)])
 
 
 class RolloutPostArgs(C.Structure):
@@ -70,7 +73,21 @@ class RolloutPostArgs(C.Structure):
         'trans', 'root_orient', 'pose_body', 'joints', 'contacts_conf', 'contacts', 'cam_trans', 'cam_root_orient',
         'g_trans', 'g_root_orient', 'g_pose_body', 'g_joints', 'g_contacts_conf', 'g_cam_trans', 'g_cam_root_orient',
         'g_world', 'g_trans0', 'g_root0', 'g_pose0', 'g_joints0', 'g_c2p_R', 'g_c2p_t', 'partial',
-        'sum_src', 'sum_add1', 'sum_add2', 'sum_out')] + [('sum_W', C.c_int)]
+        'sum_src', 'sum_add1', 'sum_add2', 'sum_out')] + [('sum_W', C.c_int)] + [
+        # turn-around riders (ABI 8)
+        ('lay_g_mu', C.c_void_p), ('lay_g_var', C.c_void_p), ('lay_pri_out', C.c_void_p), ('lay_dst', C.c_void_p), ('lay_step_stride', C.c_int64),
+        ('lay_RT', C.c_int), ('lay_pad', C.c_int), ('clr', C.c_void_p), ('clr_words', C.c_int64)]
+
+
+# ha_tune_set("turn_merge") bits and the flags of ha_humor_rollout_forward_fl / _backward_fl
+TURN_DZ, TURN_POST, TURN_FWD_CLEAR = 1, 2, 4
+ROLL_CLEARED, ROLL_LAID_OUT, ROLL_DEFER_DZ = 1, 2, 4
+
+
+class TurnTasks(C.Structure):
+    """ha_turn_tasks (include/humor_amd.h)."""
+    _fields_ = [('flags', C.c_uint), ('clr', C.c_void_p), ('clr_words', C.c_int64), ('lay_pri_out', C.c_void_p), ('lay_dst', C.c_void_p),
+                ('lay_step_stride', C.c_int64), ('lay_RT', C.c_int), ('lay_pad', C.c_int), ('dz_part', C.c_void_p), ('dz_slots', C.c_int)]
 
 
 class RigidImageArgs(C.Structure):
@@ -86,6 +103,7 @@ _SIGS = {
     'ha_device_arch': (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     'ha_tune_set': (C.c_int, [C.c_char_p, C.c_int]),
     'ha_debug_cu_poison': (C.c_int, [C.c_uint, C.POINTER(C.c_uint), C.c_void_p]),
+    'ha_debug_launch_count': (C.c_int, [C.POINTER(C.c_ulonglong)]),
     'ha_smpl_model_create': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
     'ha_smpl_model_destroy': (C.c_int, [C.c_void_p]),
     'ha_smpl_model_info': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
@@ -115,6 +133,9 @@ _SIGS = {
     'ha_humor_net_destroy': (C.c_int, [C.c_void_p]),
     'ha_humor_rollout_workspace': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     'ha_humor_rollout_forward': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]),
+    'ha_humor_rollout_forward_fl': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_uint, C.c_void_p]),
+    'ha_humor_rollout_backward_fl': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_uint, C.c_void_p]),
+    'ha_humor_rollout_turn_tasks': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(TurnTasks)]),
     'ha_humor_rollout_sample': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p]),
     'ha_humor_rollout_smpl_joints': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [c_int_p] + [C.c_void_p] * 5 + [C.c_void_p]),
     'ha_humor_rollout_smpl_joints_fwd': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [c_int_p] + [C.c_void_p] * 4 + [C.c_void_p]),

@@ -42,9 +42,11 @@ static __global__ void zero_words_kernel(unsigned* __restrict__ p, size_t n) {
 // Every kernel launch of the library goes through HA_LAUNCH: with ha_tune_set("cu_poison") (test tier, debug.hip) a kernel that fills the LDS and
 // the vector registers of every CU with a bit pattern runs in front of it -- a kernel that reads state it did not write then fails on every box.
 extern unsigned g_cu_poison;
+extern unsigned long long g_launches;      // kernel launches of the library so far (ha_debug_launch_count; one host thread per device: no lock)
 int cu_poison_launch(hipStream_t st);
 #define HA_LAUNCH(kernel, grid, block, lds, st, ...)                          \
   do {                                                                        \
+    ++ha::g_launches;                                                         \
     if (ha::g_cu_poison) (void)ha::cu_poison_launch(st);                      \
     hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);            \
   } while (0)

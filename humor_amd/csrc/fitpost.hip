@@ -10,7 +10,11 @@
 // order by a second small launch: no atomics.
 #include <string.h>
 
+#include <mutex>
+#include <unordered_map>
+
 #include "rot_math.h"
+#include "turn_dev.h"
 
 namespace ha {
 
@@ -203,12 +207,29 @@ constexpr int POST_LD = (POST_CH * NPART + 255) / 256;      // loads per thread 
 // rollout_post_reduce_kernel and the optional row-sum task (ha_seq_sum_add's work) in one launch of 256-thread blocks.
 // Blocks < B: the sequence's T x 15 partials are contiguous -- all threads fetch a chunk of POST_CH frames at once (independent, coalesced
 // loads instead of one dependent load per frame and lane), lanes < 15 then add in ascending t as rollout_post_reduce_kernel does.
-// Blocks >= B: seq_sum_add_block for sequence blockIdx.x - B.
+// The next B blocks (with sum_src): seq_sum_add_block for one sequence each.
+// Then the turn-around riders (turn_dev.h; the host passes their fields only when they ride): one block per four (row, step) pairs of the prior
+// adjoint's layout pass -- a wave each, as prior_io_kernel's blocks -- and one block per TURN_CLR_WORDS exchange words to clear.
 __global__ __launch_bounds__(256) void rollout_post_sums_kernel(ha_rollout_post_args a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];     // [POST_CH][15] | [4][64]
   const int T = a.S + 1, i = threadIdx.x;
   if ((int)blockIdx.x >= a.B) {
-    seq_sum_add_block(a.sum_src, a.sum_add1, a.sum_add2, a.sum_out, blockIdx.x - a.B, T, a.sum_W, smem);
+    int blk = blockIdx.x - a.B;
+    const int nsum = a.sum_src ? a.B : 0;
+    if (blk < nsum) {
+      seq_sum_add_block(a.sum_src, a.sum_add1, a.sum_add2, a.sum_out, blk, T, a.sum_W, smem);
+      return;
+    }
+    blk -= nsum;
+    const int rows = a.lay_RT * 32, items = a.lay_dst ? rows * a.S : 0, nlay = (items + 3) >> 2;
+    if (blk < nlay) {
+      const int item = blk * 4 + (i >> 6);
+      if (item < items)
+        prior_adjoint_rows(a.lay_g_mu, a.lay_g_var, a.lay_pri_out, (size_t)a.lay_step_stride, 1, a.lay_pad, a.lay_dst, a.B, a.S, a.lay_RT,
+                           item % rows, item / rows, i & 63);
+      return;
+    }
+    zero_words_block(reinterpret_cast<unsigned*>(a.clr), (size_t)a.clr_words, blk - nlay);
     return;
   }
   const int b = blockIdx.x;
@@ -232,7 +253,35 @@ __global__ __launch_bounds__(256) void rollout_post_sums_kernel(ha_rollout_post_
   else a.g_trans0[(size_t)b * 3 + (i - 12)] = s;
 }
 
+// the riders as launches of their own ("turn_merge" bit HA_TURN_POST off): the grid of prior_io_kernel (rollout.hip)
+__global__ __launch_bounds__(64) void prior_layout_kernel(ha_rollout_post_args a) {
+  prior_adjoint_rows(a.lay_g_mu, a.lay_g_var, a.lay_pri_out, (size_t)a.lay_step_stride, 1, a.lay_pad, a.lay_dst, a.B, a.S, a.lay_RT,
+                     blockIdx.x, blockIdx.y, threadIdx.x);
+}
+
 extern int g_loss_merge;      // fitloss.hip
+int g_turn_merge = HA_TURN_DZ | HA_TURN_POST | HA_TURN_FWD_CLEAR;
+
+// ---- marks of the turn-around riders (turn_dev.h): region address -> what a host launch has done to it since its last use -----------
+static std::mutex g_turn_mu;
+static std::unordered_map<const void*, unsigned> g_turn_marks;
+void turn_mark(const void* p, unsigned bits) {
+  std::lock_guard<std::mutex> lk(g_turn_mu);
+  g_turn_marks[p] |= bits;
+}
+bool turn_take(const void* p, unsigned bits) {
+  std::lock_guard<std::mutex> lk(g_turn_mu);
+  const auto it = g_turn_marks.find(p);
+  if (it == g_turn_marks.end()) return false;
+  const bool all = (it->second & bits) == bits;
+  it->second &= ~bits;
+  if (!it->second) g_turn_marks.erase(it);
+  return all;
+}
+void turn_forget(const void* p) {
+  std::lock_guard<std::mutex> lk(g_turn_mu);
+  g_turn_marks.erase(p);
+}
 
 }  // namespace ha
 
@@ -259,15 +308,36 @@ extern "C" int ha_rollout_post_backward(const ha_rollout_post_args* args, void* 
   HA_REQUIRE(a.g_world && a.g_trans0 && a.g_root0 && a.g_pose0 && a.g_joints0 && a.partial, "ha_rollout_post_backward: null output");
   HA_REQUIRE(!a.c2p_R || (a.g_c2p_R && a.g_c2p_t), "ha_rollout_post_backward: cam2prior gradient outputs missing");
   HA_REQUIRE(!a.sum_src || (a.sum_out && a.sum_W >= 1 && a.sum_W <= 64), "ha_rollout_post_backward: the row-sum task needs sum_out and 1 <= sum_W <= 64");
+  HA_REQUIRE(!a.lay_dst || (a.lay_pri_out && a.lay_RT == (a.B + 31) / 32 && a.lay_pad >= 2 * TURN_ZD && a.lay_pad % 4 == 0 && a.lay_step_stride >= 0 &&
+                            (int64_t)a.lay_RT * 32 * a.S < ((int64_t)1 << 29)),
+             "ha_rollout_post_backward: the layout task needs lay_pri_out, lay_RT = ceil(B / 32) and lay_pad >= 96, a multiple of 4");
+  HA_REQUIRE(!a.clr || (a.clr_words >= 1 && a.clr_words < ((int64_t)1 << 31)), "ha_rollout_post_backward: the clear task needs 1 <= clr_words < 2^31");
   hipStream_t st = (hipStream_t)stream;
+  const bool ride = g_loss_merge && (g_turn_merge & HA_TURN_POST);
   if (a.sum_src && !g_loss_merge) {
     const int rc = ha_seq_sum_add(a.B, a.S + 1, a.sum_W, a.sum_src, a.sum_add1, a.sum_add2, a.sum_out, stream);
     if (rc != HA_OK) return rc;
   }
   HA_LAUNCH(rollout_post_bwd_kernel, dim3(a.B * (a.S + 1)), dim3(64), 0, st, a);
   HA_LAUNCH_CHECK();
-  if (g_loss_merge) HA_LAUNCH(rollout_post_sums_kernel, dim3(a.B * (a.sum_src ? 2 : 1)), dim3(256), POST_CH * NPART * sizeof(float), st, a);
-  else HA_LAUNCH(rollout_post_reduce_kernel, dim3(a.B), dim3(64), 0, st, a);
+  if (g_loss_merge) {
+    ha_rollout_post_args k = a;
+    if (!ride) { k.lay_dst = nullptr; k.clr = nullptr; }
+    const unsigned nlay = k.lay_dst ? (unsigned)((a.lay_RT * 32 * a.S + 3) / 4) : 0u, nclr = k.clr ? zero_words_blocks((size_t)a.clr_words) : 0u;
+    HA_LAUNCH(rollout_post_sums_kernel, dim3(a.B * (a.sum_src ? 2 : 1) + nlay + nclr), dim3(256), POST_CH * NPART * sizeof(float), st, k);
+  } else HA_LAUNCH(rollout_post_reduce_kernel, dim3(a.B), dim3(64), 0, st, a);
   HA_LAUNCH_CHECK();
+  if (!ride) {
+    if (a.lay_dst) {
+      HA_LAUNCH(prior_layout_kernel, dim3(a.lay_RT * 32, a.S), dim3(64), 0, st, a);
+      HA_LAUNCH_CHECK();
+    }
+    if (a.clr) {
+      zero_async(a.clr, (size_t)a.clr_words * 4, st);
+      HA_LAUNCH_CHECK();
+    }
+  }
+  if (a.lay_dst) turn_mark(a.lay_dst, TURN_MARK_LAID);
+  if (a.clr) turn_mark(a.clr, TURN_MARK_CLEARED);
   return HA_OK;
 }

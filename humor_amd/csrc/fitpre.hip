@@ -8,9 +8,12 @@
 // evaluation remains; the translated root lands on (0, 0, root_height - j0.z) exactly as in the reference (its R (trans + t)
 // with t = -trans is identically zero).  ~230 element-wise launches (forward + autograd backward) and two SMPL calls per
 // closure become two launches.  One wavefront per sequence; lane j < 22 owns SMPL joint j (and body rotation j - 1).
+// Blocks beyond the B sequences are turn-around riders (turn_dev.h): the forward launch clears the exchange words of the persistent roll-out
+// that follows it, the backward launch adds up the dL/dz partials the persistent adjoint in front of it left.
 #include <string.h>
 
 #include "rot_math.h"
+#include "turn_dev.h"
 
 namespace ha {
 
@@ -65,6 +68,10 @@ __device__ __forceinline__ void c2p_forward(const float floor[3], const float tr
 }
 
 __global__ __launch_bounds__(64) void fit_pre_fwd_kernel(ha_fit_pre_args a) {
+  if ((int)blockIdx.x >= a.B) {                   // rider: nothing here reads or writes what the sequence blocks touch
+    zero_words_block(reinterpret_cast<unsigned*>(a.clr), (size_t)a.clr_words, blockIdx.x - a.B);
+    return;
+  }
   const int b = blockIdx.x, j = threadIdx.x;
   const float* floor = a.floor + (size_t)b * 3;
   const float* trans = a.trans0 + (size_t)b * 3;
@@ -117,7 +124,17 @@ __global__ __launch_bounds__(64) void fit_pre_fwd_kernel(ha_fit_pre_args a) {
   }
 }
 
+// the dL/dz reduction as a launch of its own ("turn_merge" bit HA_TURN_DZ off)
+__global__ __launch_bounds__(256) void dz_reduce_task_kernel(const float* __restrict__ part, float* __restrict__ g_z, const float* __restrict__ g_z_add,
+                                                             int B, int S) {
+  dz_reduce_elem(part, g_z, g_z_add, B, S, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 __global__ __launch_bounds__(64) void fit_pre_bwd_kernel(ha_fit_pre_args a) {
+  if ((int)blockIdx.x >= a.B) {                   // rider: g_z is a leaf gradient, the sequence blocks read the adjoint's dL/d(initial state)
+    dz_reduce_elem(a.dz_part, a.dz_g_z, a.dz_g_z_add, a.dz_B, a.dz_S, (int)(blockIdx.x - a.B) * 64 + (int)threadIdx.x);
+    return;
+  }
   const int b = blockIdx.x, j = threadIdx.x;
   const float* floor = a.floor + (size_t)b * 3;
   const float* trans = a.trans0 + (size_t)b * 3;
@@ -285,8 +302,16 @@ extern "C" int ha_fit_pre_forward(const ha_fit_pre_args* args, void* stream) {
   HA_REQUIRE(a.B >= 1, "ha_fit_pre_forward: B must be >= 1");
   HA_REQUIRE(a.floor && a.trans0 && a.root0 && a.pose0 && a.jcam && a.trans_vel && a.joints_vel && a.root_orient_vel, "ha_fit_pre_forward: null input");
   HA_REQUIRE(a.past_in && a.trans_p && a.root_p && a.joints_p && a.c2p_R && a.c2p_t && a.root_height, "ha_fit_pre_forward: null output");
-  HA_LAUNCH(fit_pre_fwd_kernel, dim3(a.B), dim3(64), 0, (hipStream_t)stream, a);
+  HA_REQUIRE(!a.clr || (a.clr_words >= 1 && a.clr_words < ((int64_t)1 << 31)), "ha_fit_pre_forward: the clear task needs 1 <= clr_words < 2^31");
+  hipStream_t st = (hipStream_t)stream;
+  const bool ride = a.clr && (g_turn_merge & HA_TURN_FWD_CLEAR);
+  if (a.clr && !ride) {
+    zero_async(a.clr, (size_t)a.clr_words * 4, st);
+    HA_LAUNCH_CHECK();
+  }
+  HA_LAUNCH(fit_pre_fwd_kernel, dim3(a.B + (ride ? zero_words_blocks((size_t)a.clr_words) : 0u)), dim3(64), 0, st, a);
   HA_LAUNCH_CHECK();
+  if (a.clr) turn_mark(a.clr, TURN_MARK_CLEARED);
   return HA_OK;
 }
 
@@ -297,7 +322,17 @@ extern "C" int ha_fit_pre_backward(const ha_fit_pre_args* args, void* stream) {
   HA_REQUIRE(a.floor && a.trans0 && a.root0 && a.pose0 && a.jcam, "ha_fit_pre_backward: null input");
   HA_REQUIRE(a.g_floor && a.g_trans0 && a.g_root0 && a.g_pose0 && a.g_jcam && a.g_trans_vel && a.g_joints_vel && a.g_root_orient_vel,
              "ha_fit_pre_backward: null gradient output");
-  HA_LAUNCH(fit_pre_bwd_kernel, dim3(a.B), dim3(64), 0, (hipStream_t)stream, a);
+  HA_REQUIRE(!a.dz_part || (a.dz_g_z && a.dz_B >= 1 && a.dz_B <= 32 && a.dz_S >= 1 && a.dz_slots == TURN_DZ_SLOTS && (int64_t)a.dz_B * a.dz_S * TURN_ZD < ((int64_t)1 << 31)),
+             "ha_fit_pre_backward: the dz task needs dz_g_z, 1 <= dz_B <= 32, dz_S >= 1 and dz_slots = %d", TURN_DZ_SLOTS);
+  hipStream_t st = (hipStream_t)stream;
+  const int nz = a.dz_part ? a.dz_B * a.dz_S * TURN_ZD : 0;
+  const bool ride = a.dz_part && (g_turn_merge & HA_TURN_DZ);
+  if (a.dz_part && !ride) {
+    HA_LAUNCH(dz_reduce_task_kernel, dim3(ceil_div(nz, 256)), dim3(256), 0, st, a.dz_part, a.dz_g_z, a.dz_g_z_add, a.dz_B, a.dz_S);
+    HA_LAUNCH_CHECK();
+  }
+  HA_LAUNCH(fit_pre_bwd_kernel, dim3(a.B + (ride ? ceil_div(nz, 64) : 0)), dim3(64), 0, st, a);
   HA_LAUNCH_CHECK();
+  if (a.dz_part) (void)turn_take(a.dz_part, TURN_MARK_DZ_PENDING);      // picked up: the roll-out entry points of the network are open again
   return HA_OK;
 }

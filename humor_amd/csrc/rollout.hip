@@ -24,6 +24,7 @@
 
 #include "rollout_persist.h"
 #include "rot_math.h"
+#include "turn_dev.h"
 
 namespace ha {
 
@@ -44,9 +45,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float vf4 __attribute__((ext_vector_type(4)));
 typedef float vf2 __attribute__((ext_vector_type(2)));
 
-// offset of channel c inside one row's view of a quad-interleaved tile: element (c, row) of tile rt of a C-channel slab
-// (C % 4 == 0) is slab[rt * C * 32 + row * 4 + qoff(c)]
-__device__ __forceinline__ size_t qoff(int c) { return (size_t)(c >> 2) * 128 + (c & 3); }
+// (qoff -- the offset of a channel inside a row's view of a quad-interleaved tile -- and slab_sum: turn_dev.h)
+static_assert(TURN_ZD == ZD, "turn_dev.h restates the latent width");
 
 // ha_tune_set "layer_finish": GroupNorm prologues in a finishing pass (gn_finish_kernel) -- 1 (default) from two row tiles on, 0 never, 2 always
 int g_layer_finish = 1;
@@ -97,6 +97,7 @@ struct CallPlan {
   int ngroups = 1, rows_per_group = 0;
   size_t group_floats = 0;     // stash stride between row groups (0 with one group)
   const float* g_z_add = nullptr;   // backward only: the dL/dz addend, when the one-launch adjoint adds it in its final reduction
+  unsigned turn = 0;                // HA_ROLL_* flags of this call (turn-around riders: what a neighbouring launch does in this call's place)
 };
 
 struct PackedLayer {
@@ -124,7 +125,10 @@ struct ha_humor_net {
   // A forward overwrites the record of its address and makes it the newest; beyond MAX_STASH_RECS records the oldest go first.
   // A backward leaves the record in place: a second backward over a retained graph finds it again.
   // feedback: filled by ha_humor_rollout_smpl_joints_fwd -- only ha_humor_rollout_smpl_joints_bwd may read it, and it reads no other
+  // (plan.turn: the HA_ROLL_* flags the forward call ran with)
   struct StashRec { ha::CallPlan plan; int B, S, knobs; bool feedback; std::list<const void*>::iterator age; };
+  // dL/dz partials a backward call left unreduced (HA_ROLL_DEFER_DZ) and that no ha_fit_pre_backward has picked up yet (turn_dev.h), or null
+  mutable const void* dz_pending = nullptr;
   static constexpr size_t MAX_STASH_RECS = 65536;
   mutable std::unordered_map<const void*, StashRec> stash_recs;
   mutable std::list<const void*> stash_age;   // oldest first
@@ -155,22 +159,7 @@ struct LayerLaunch {
   int RT;
 };
 
-constexpr int SPB = 4;        // K-slices per block of a layer launch
-constexpr int MAXSPLIT = 5;   // K-slices / SPB never exceeds this for the supported layer widths (K <= 1280)
-
-// sums `nsplit` (<= MAXSPLIT) partial slabs of element (channel c, row) of tile rt.  All loads are unconditional (clamped
-// slab index, zero weight beyond nsplit) so they issue back-to-back instead of one round trip per slab.
-__device__ __forceinline__ float slab_sum(const float* base, int nsplit, int RT, int C, int rt, int c, int row) {
-  const size_t stride = (size_t)RT * C * 32;
-  const float* p = base + (size_t)rt * C * 32 + (size_t)row * 4 + qoff(c);
-  float t[MAXSPLIT];
-#pragma unroll
-  for (int s = 0; s < MAXSPLIT; ++s) t[s] = p[(size_t)(s < nsplit ? s : 0) * stride];
-  float v = t[0];
-#pragma unroll
-  for (int s = 1; s < MAXSPLIT; ++s) v += s < nsplit ? t[s] : 0.f;
-  return v;
-}
+constexpr int SPB = 4;        // K-slices per block of a layer launch (MAXSPLIT, the most partial slabs slab_sum adds: turn_dev.h)
 
 // A wave's 64-channel x 32-row fragment of a slab stack: lane (row, hi) reads channels cbase + 32 hi + kp as eight quads.
 // All NS x 8 16-byte loads are issued back-to-back (independent) and summed in split order.  nq = number of quads that
@@ -1077,24 +1066,16 @@ struct PriorIOParams {
 
 __global__ __launch_bounds__(64) void prior_io_kernel(PriorIOParams p) {
   const int r = blockIdx.x, t = blockIdx.y, lane = threadIdx.x;
-  const int rt = r >> 5, rr = r & 31;
-  const float* po = p.pri_out0 + (size_t)t * p.step_stride;
-  float mu = 0.f, var = 0.f;
-  if (r < p.B && lane < ZD) {
-    mu = slab_sum(po, p.pri_nsplit, p.RT, p.pri_pad, rt, lane, rr);
-    var = expf(slab_sum(po, p.pri_nsplit, p.RT, p.pri_pad, rt, ZD + lane, rr));
+  if (p.prior_mu && r < p.B && lane < ZD) {
+    const int rt = r >> 5, rr = r & 31;
+    const float* po = p.pri_out0 + (size_t)t * p.step_stride;
+    const size_t o = ((size_t)r * p.S + t) * ZD + lane;
+    p.prior_mu[o] = slab_sum(po, p.pri_nsplit, p.RT, p.pri_pad, rt, lane, rr);
+    p.prior_var[o] = expf(slab_sum(po, p.pri_nsplit, p.RT, p.pri_pad, rt, ZD + lane, rr));
   }
-  const size_t o = ((size_t)r * p.S + t) * ZD + lane;
-  if (p.prior_mu && r < p.B && lane < ZD) { p.prior_mu[o] = mu; p.prior_var[o] = var; }
-  if (p.g_pri_all) {
-    float* GP = p.g_pri_all + ((size_t)t * p.RT + rt) * p.pri_pad * 32 + (size_t)rr * 4;
-    if (lane < ZD) {
-      const bool live = r < p.B;
-      GP[qoff(lane)] = (live && p.g_prior_mu) ? p.g_prior_mu[o] : 0.f;
-      GP[qoff(ZD + lane)] = (live && p.g_prior_var) ? p.g_prior_var[o] * var : 0.f;
-    }
-    for (int c = 2 * ZD + lane; c < p.pri_pad; c += 64) GP[qoff(c)] = 0.f;
-  }
+  // the adjoint branch: shared with ha_rollout_post_backward, which can run it as a block role (turn_dev.h)
+  if (p.g_pri_all)
+    prior_adjoint_rows(p.g_prior_mu, p.g_prior_var, p.pri_out0, p.step_stride, p.pri_nsplit, p.pri_pad, p.g_pri_all, p.B, p.S, p.RT, r, t, lane);
 }
 
 // [B][S][C] -> [S][RT][Cp/4][32][4] (quad-interleaved tiles, zero-padded rows and channels); Cp = C rounded up to 4
@@ -1825,6 +1806,7 @@ static int rollout_forward_impl(const ha_humor_net* net, const CallPlan& plan, c
       f.hidden_slabs = plan.path != Path::one_launch_lean;
       f.t2j = stash + L.t2j;
       f.ws = stash + L.persist_ws;
+      f.ws_cleared = (plan.turn & HA_ROLL_CLEARED) != 0;
       return persist_forward(net->persist, f, ((g_rollout_persist >> 1) & 1) | (g_rollout_persist_inject ? 2 : 0), st);
     }
     if (phase == PH_STEP) return HA_OK;
@@ -1989,9 +1971,11 @@ extern "C" int ha_humor_rollout_smpl_joints(const ha_humor_net* net, int B, int 
 }
 
 // dL/d(prior_mu, prior_var) of all steps -> gx_pri (dL/dx_t through the prior network)
+// (laid_out: a launch in front has already written the g_pri_out slab as a block role -- turn_dev.h)
 static int prior_adjoint_all(const ha_humor_net* net, const StashLayout& L, int B, int S, const float* g_prior_mu, const float* g_prior_var,
-                             float* stash, hipStream_t st) {
+                             float* stash, hipStream_t st, bool laid_out) {
   const int np = net->n_pri, RT = L.RT;
+  if (laid_out) return prior_backward_batched(net, L, stash, S, st);
   PriorIOParams q;
   memset(&q, 0, sizeof(q));
   q.B = B; q.S = S; q.RT = RT;
@@ -2019,7 +2003,7 @@ static int rollout_backward_impl(const ha_humor_net* net, const CallPlan& plan, 
 
   // the prior's contribution to dL/dx_t for every step, before the reverse scan (it does not depend on the scan)
   if (with_prior && phase == PH_BEGIN) {
-    int rc = prior_adjoint_all(net, L, B, S, g_prior_mu, g_prior_var, stash, st);
+    int rc = prior_adjoint_all(net, L, B, S, g_prior_mu, g_prior_var, stash, st, (plan.turn & HA_ROLL_LAID_OUT) != 0);
     if (rc != HA_OK) return rc;
   }
 
@@ -2068,6 +2052,8 @@ static int rollout_backward_impl(const ha_humor_net* net, const CallPlan& plan, 
       f.g_past0 = g_past_in0; f.g_z = g_z_seq; f.g_z_add = plan.g_z_add;
       f.dz_part = stash + L.dz_part;
       f.ws = stash + L.persist_ws;
+      f.ws_cleared = (plan.turn & HA_ROLL_CLEARED) != 0;
+      f.defer_dz = (plan.turn & HA_ROLL_DEFER_DZ) != 0;
       return persist_backward(net->persist, f, (g_rollout_persist >> 1) & 1, st);
     }
     return HA_OK;
@@ -2196,11 +2182,69 @@ static void record_stash(const ha_humor_net* net, const float* stash, const Call
   it->second.plan = plan; it->second.B = B; it->second.S = S; it->second.knobs = layout_knobs(); it->second.feedback = feedback;
 }
 
+// ---- turn-around riders (turn_dev.h; the header's "Turn-around riders") -------------------------------
+// the one plan whose short launches may ride elsewhere: the B <= 32 persistent kernels serving the whole call
+static bool turn_plan_fits(const CallPlan& plan, int B) { return plan.path != Path::chain && !plan.piped && plan.ngroups == 1 && B <= 32; }
+
+// dL/dz partials left unreduced by an earlier backward call and never picked up: an error, once
+static int turn_check_pending(const ha_humor_net* net, const char* who) {
+  if (!net->dz_pending) return HA_OK;
+  const bool still = turn_take(net->dz_pending, TURN_MARK_DZ_PENDING);
+  net->dz_pending = nullptr;
+  HA_REQUIRE(!still, "%s: an earlier ha_humor_rollout_backward_fl on this network left its dL/dz partials unreduced (HA_ROLL_DEFER_DZ) and no "
+             "ha_fit_pre_backward has picked them up: the g_z_seq of that call was never written", who);
+  return HA_OK;
+}
+
+extern "C" int ha_humor_rollout_turn_tasks(const ha_humor_net* net, int B, int S, float* stash, int adjoint, ha_turn_tasks* out) {
+  HA_REQUIRE(net && stash && out, "ha_humor_rollout_turn_tasks: null argument");
+  HA_REQUIRE(B >= 1 && S >= 1, "ha_humor_rollout_turn_tasks: B and S must be >= 1");
+  memset(out, 0, sizeof(*out));
+  if (!adjoint) {
+    const CallPlan plan = rollout_plan(net, B, S);
+    if (!(g_turn_merge & HA_TURN_FWD_CLEAR) || !turn_plan_fits(plan, B)) return HA_OK;
+    StashLayout L;
+    make_layout(net, B, S, plan.path, L);
+    out->clr = stash + L.persist_ws; out->clr_words = (int64_t)persist_ws_floats();
+    out->flags = HA_ROLL_CLEARED;
+    return HA_OK;
+  }
+  const auto it = net->stash_recs.find(stash);
+  HA_REQUIRE(it != net->stash_recs.end(), "ha_humor_rollout_turn_tasks: no forward call of this network has filled this stash");
+  const ha_humor_net::StashRec& rec = it->second;
+  HA_REQUIRE(rec.B == B && rec.S == S, "ha_humor_rollout_turn_tasks: the stash was filled by a forward call of %d x %d, not %d x %d", rec.B, rec.S, B, S);
+  if (rec.feedback || rec.knobs != layout_knobs() || !turn_plan_fits(rec.plan, B) || !adjoint_one_launch(rec.plan, B)) return HA_OK;
+  StashLayout L;
+  make_layout(net, B, S, rec.plan.path, L);
+  if (g_turn_merge & HA_TURN_POST) {
+    const int np = net->n_pri;
+    out->clr = stash + L.persist_ws; out->clr_words = (int64_t)persist_ws_floats();
+    out->lay_pri_out = stash + L.pri_h[np - 1]; out->lay_dst = stash + L.g_pri_out;
+    out->lay_RT = L.RT; out->lay_pad = net->pri[np - 1].Nout_pad; out->lay_step_stride = (int64_t)L.RT * out->lay_pad * 32;
+    out->flags |= HA_ROLL_CLEARED | HA_ROLL_LAID_OUT;
+  }
+  if (g_turn_merge & HA_TURN_DZ) {
+    out->dz_part = stash + L.dz_part; out->dz_slots = persist_dz_slots();
+    out->flags |= HA_ROLL_DEFER_DZ;
+  }
+  return HA_OK;
+}
+
 extern "C" int ha_humor_rollout_forward(const ha_humor_net* net, int B, int S, const float* past_in0, const float* z_seq,
                                         float* world, float* prior_mu, float* prior_var, float* stash, void* stream) {
+  return ha_humor_rollout_forward_fl(net, B, S, past_in0, z_seq, world, prior_mu, prior_var, stash, 0u, stream);
+}
+
+extern "C" int ha_humor_rollout_forward_fl(const ha_humor_net* net, int B, int S, const float* past_in0, const float* z_seq,
+                                           float* world, float* prior_mu, float* prior_var, float* stash, unsigned int flags, void* stream) {
   HA_REQUIRE(net && past_in0 && z_seq && world && stash, "ha_humor_rollout_forward: null argument");
   HA_REQUIRE(B >= 1 && S >= 1, "ha_humor_rollout_forward: B and S must be >= 1");
   HA_REQUIRE((prior_mu == nullptr) == (prior_var == nullptr), "ha_humor_rollout_forward: prior_mu and prior_var go together");
+  HA_REQUIRE((flags & ~HA_ROLL_CLEARED) == 0, "ha_humor_rollout_forward: flags 0x%x: only HA_ROLL_CLEARED applies to the forward call", flags);
+  {
+    const int rc = turn_check_pending(net, "ha_humor_rollout_forward");
+    if (rc != HA_OK) return rc;
+  }
   if (persist_take_failure(net->persist)) {
     set_error("ha_humor_rollout_forward: an earlier persistent roll-out launch on this network failed (error word 0x%x: its bounded waits ran out -- was "
               "another kernel holding part of the GPU?); the results of that call are invalid.  This network now uses the launch chain.",
@@ -2208,7 +2252,17 @@ extern "C" int ha_humor_rollout_forward(const ha_humor_net* net, int B, int S, c
     return HA_ERR_HIP;
   }
   DeviceGuard guard(net->device);
-  const CallPlan plan = rollout_plan(net, B, S);
+  CallPlan plan = rollout_plan(net, B, S);
+  if (turn_plan_fits(plan, B)) {
+    StashLayout L;
+    make_layout(net, B, S, plan.path, L);
+    const bool cleared = turn_take(stash + L.persist_ws, TURN_MARK_CLEARED);      // (a mark is good for one call)
+    HA_REQUIRE(!(flags & HA_ROLL_CLEARED) || cleared, "ha_humor_rollout_forward: HA_ROLL_CLEARED, but no launch has cleared the exchange words of this "
+               "stash since their last use (ha_fit_pre_forward with the clr task of ha_humor_rollout_turn_tasks does)");
+  } else
+    HA_REQUIRE(!flags, "ha_humor_rollout_forward: HA_ROLL_CLEARED, but this call does not run the B <= 32 persistent kernel "
+               "(ha_humor_rollout_turn_tasks says when it does)");
+  plan.turn = flags;
   record_stash(net, stash, plan, B, S, false);
   return for_each_group(net, plan, B, S, false, (hipStream_t)stream, [&](int g, int r0, int rows, const StashLayout& L, hipStream_t st, int phase, int t) {
     const size_t r = (size_t)r0;
@@ -2227,15 +2281,26 @@ __global__ void add_inplace_kernel(float* __restrict__ dst, const float* __restr
 extern "C" int ha_humor_rollout_backward(const ha_humor_net* net, int B, int S, const float* z_seq, const float* g_world,
                                          const float* g_prior_mu, const float* g_prior_var, float* stash, float* g_past_in0,
                                          float* g_z_seq, void* stream) {
-  return ha_humor_rollout_backward_ex(net, B, S, z_seq, g_world, g_prior_mu, g_prior_var, stash, g_past_in0, g_z_seq, nullptr, stream);
+  return ha_humor_rollout_backward_fl(net, B, S, z_seq, g_world, g_prior_mu, g_prior_var, stash, g_past_in0, g_z_seq, nullptr, 0u, stream);
 }
 
 extern "C" int ha_humor_rollout_backward_ex(const ha_humor_net* net, int B, int S, const float* z_seq, const float* g_world,
                                             const float* g_prior_mu, const float* g_prior_var, float* stash, float* g_past_in0,
                                             float* g_z_seq, const float* g_z_add, void* stream) {
+  return ha_humor_rollout_backward_fl(net, B, S, z_seq, g_world, g_prior_mu, g_prior_var, stash, g_past_in0, g_z_seq, g_z_add, 0u, stream);
+}
+
+extern "C" int ha_humor_rollout_backward_fl(const ha_humor_net* net, int B, int S, const float* z_seq, const float* g_world,
+                                            const float* g_prior_mu, const float* g_prior_var, float* stash, float* g_past_in0,
+                                            float* g_z_seq, const float* g_z_add, unsigned int flags, void* stream) {
   HA_REQUIRE(net && stash && g_past_in0 && g_z_seq, "ha_humor_rollout_backward: null argument");
   HA_REQUIRE(B >= 1 && S >= 1, "ha_humor_rollout_backward: B and S must be >= 1");
+  HA_REQUIRE((flags & ~(HA_ROLL_CLEARED | HA_ROLL_LAID_OUT | HA_ROLL_DEFER_DZ)) == 0, "ha_humor_rollout_backward: unknown flag bits 0x%x", flags);
   (void)z_seq;
+  {
+    const int rc = turn_check_pending(net, "ha_humor_rollout_backward");
+    if (rc != HA_OK) return rc;
+  }
   if (persist_take_failure(net->persist)) {
     set_error("ha_humor_rollout_backward: an earlier persistent roll-out launch on this network failed (error word 0x%x); its results are invalid.  "
               "This network now uses the launch chain.", persist_error_word(net->persist));
@@ -2256,7 +2321,27 @@ extern "C" int ha_humor_rollout_backward_ex(const ha_humor_net* net, int B, int 
              "ha_humor_rollout_backward: this stash was filled by a persistent / pipelined forward without launch-chain slabs (only the one-launch "
              "adjoint can read it) and the persistent path has been disabled since (a launch reported a failure, error word 0x%x): repeat the "
              "forward call -- it will run on the launch chain", persist_error_word(net->persist));
+  // turn-around riders: what launches around this call have done or will do in its place -- each claim checked against the riding launch's mark
+  plan.turn = 0;
+  if (turn_plan_fits(plan, B) && adjoint_one_launch(plan, B)) {
+    StashLayout L;
+    make_layout(net, B, S, plan.path, L);
+    const bool cleared = turn_take(stash + L.persist_ws, TURN_MARK_CLEARED), laid = turn_take(stash + L.g_pri_out, TURN_MARK_LAID);
+    HA_REQUIRE(!(flags & HA_ROLL_CLEARED) || cleared, "ha_humor_rollout_backward: HA_ROLL_CLEARED, but no launch has cleared the exchange words of this "
+               "stash since their last use (ha_rollout_post_backward with the clr task of ha_humor_rollout_turn_tasks does)");
+    HA_REQUIRE(!(flags & HA_ROLL_LAID_OUT) || laid, "ha_humor_rollout_backward: HA_ROLL_LAID_OUT, but no launch has laid g_prior_mu / g_prior_var out "
+               "in this stash since the last backward over it (ha_rollout_post_backward with the layout task of ha_humor_rollout_turn_tasks does)");
+    HA_REQUIRE(!(flags & HA_ROLL_LAID_OUT) || g_prior_mu || g_prior_var, "ha_humor_rollout_backward: HA_ROLL_LAID_OUT without g_prior_mu / g_prior_var");
+    plan.turn = flags;
+    if (flags & HA_ROLL_DEFER_DZ) {
+      turn_mark(stash + L.dz_part, TURN_MARK_DZ_PENDING);
+      net->dz_pending = stash + L.dz_part;
+    }
+  } else
+    HA_REQUIRE(!flags, "ha_humor_rollout_backward: flags 0x%x, but the adjoint over this stash does not run the B <= 32 persistent kernel "
+               "(ha_humor_rollout_turn_tasks says when it does)", flags);
   // dL/dz += g_z_add: in the one-launch adjoint's final reduction when it serves the whole call, else add_inplace_kernel afterwards
+  // (HA_ROLL_DEFER_DZ: the launch that reduces the partials is given the addend)
   if (g_z_add && plan.ngroups == 1 && adjoint_one_launch(plan, B)) plan.g_z_add = g_z_add;
   const int rc = for_each_group(net, plan, B, S, true, (hipStream_t)stream, [&](int g, int r0, int rows, const StashLayout& L, hipStream_t st, int phase, int t) {
     const size_t r = (size_t)r0;

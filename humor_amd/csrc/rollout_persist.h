@@ -22,6 +22,7 @@ struct PersistFwd {
   bool hidden_slabs = true;                   // B > 32: also write the hidden pre-activations as launch-chain slabs (for the launch-chain adjoint)
   float* t2j = nullptr;              // [32][3]
   float* ws = nullptr;               // persist_ws_floats() floats of exchange space (zeroed by persist_forward before the launch)
+  bool ws_cleared = false;           // B <= 32: a launch in front on the same stream has zeroed ws (a turn-around rider): no clear launch here
 };
 
 // The adjoint of the same roll-out: reads the forward's stash (states, decoder pre-activations, GroupNorm statistics, glue
@@ -41,6 +42,8 @@ struct PersistBwd {
   const float* g_z_add = nullptr;    // [B][S][48] or null: added to g_z by the final reduction (the gradient another reader of z produced)
   float* dz_part = nullptr;          // [S][persist_dz_slots()][32][48]
   float* ws = nullptr;
+  bool ws_cleared = false;           // B <= 32: as PersistFwd::ws_cleared
+  bool defer_dz = false;             // B <= 32: leave dz_part unreduced (g_z unwritten): a launch behind on the same stream reduces it
 };
 
 size_t persist_ws_floats();

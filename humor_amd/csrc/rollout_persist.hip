@@ -32,6 +32,7 @@
 
 #include "rot_math.h"
 #include "lane_reduce.h"
+#include "turn_dev.h"
 
 namespace ha {
 
@@ -1777,13 +1778,10 @@ __global__ __launch_bounds__(256) HA_WAVES_PER_EU(1, 1) void rollout_persist_bwd
 
 
 // g_z[b][t][c] = sum of the DZ_SLOTS partial products, fixed order
+// (the body is shared with ha_fit_pre_backward, which can run it as a block role: turn_dev.h)
+static_assert(DZ_SLOTS == TURN_DZ_SLOTS && P_ZD == TURN_ZD, "turn_dev.h restates the shape of the dL/dz partials");
 __global__ void dz_reduce_kernel(const float* __restrict__ part, float* __restrict__ g_z, const float* __restrict__ g_z_add, int B, int S) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * S * P_ZD) return;
-  const int c = i % P_ZD, t = (i / P_ZD) % S, b = i / (P_ZD * S);
-  float v = 0.f;
-  for (int sl = 0; sl < DZ_SLOTS; ++sl) v += part[(((size_t)t * DZ_SLOTS + sl) * 32 + b) * P_ZD + c];
-  g_z[i] = g_z_add ? v + g_z_add[i] : v;
+  dz_reduce_elem(part, g_z, g_z_add, B, S, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 #include "rollout_pipe.inc"
@@ -2120,8 +2118,10 @@ int persist_forward(PersistNet* p, const PersistFwd& f, int variant, hipStream_t
     ++p->launches;
     return HA_OK;
   }
-  zero_async(f.ws, XCH_BYTES, st);        // tags, team counters (tag 0 never matches); a kernel, not a memset node: common.h
-  HA_LAUNCH_CHECK();
+  if (!f.ws_cleared) {                    // (else a launch in front has done it as a block role: turn_dev.h)
+    zero_async(f.ws, XCH_BYTES, st);      // tags, team counters (tag 0 never matches); a kernel, not a memset node: common.h
+    HA_LAUNCH_CHECK();
+  }
   PersistArgs a;
   memset(&a, 0, sizeof(a));
   a.B = f.B; a.S = f.S;
@@ -2177,8 +2177,10 @@ int persist_backward(PersistNet* p, const PersistBwd& f, int variant, hipStream_
     ++p->launches_bwd;
     return HA_OK;
   }
-  zero_async(f.ws, XCH_BYTES, st);
-  HA_LAUNCH_CHECK();
+  if (!f.ws_cleared) {
+    zero_async(f.ws, XCH_BYTES, st);
+    HA_LAUNCH_CHECK();
+  }
   PersistBwdArgs a;
   memset(&a, 0, sizeof(a));
   a.B = f.B; a.S = f.S;
@@ -2195,9 +2197,11 @@ int persist_backward(PersistNet* p, const PersistBwd& f, int variant, hipStream_
   if (variant & 1) HA_LAUNCH(rollout_persist_bwd_kernel<true>, dim3(NTEAMS * TEAM_CUS), dim3(256), LB_TOTAL * 4, st, a);
   else HA_LAUNCH(rollout_persist_bwd_kernel<false>, dim3(NTEAMS * TEAM_CUS), dim3(256), LB_TOTAL * 4, st, a);
   HA_LAUNCH_CHECK();
-  const int n = f.B * f.S * P_ZD;
-  HA_LAUNCH(dz_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)f.dz_part, f.g_z, f.g_z_add, f.B, f.S);
-  HA_LAUNCH_CHECK();
+  if (!f.defer_dz) {
+    const int n = f.B * f.S * P_ZD;
+    HA_LAUNCH(dz_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)f.dz_part, f.g_z, f.g_z_add, f.B, f.S);
+    HA_LAUNCH_CHECK();
+  }
   ++p->launches_bwd;
   return HA_OK;
 #endif

@@ -49,6 +49,7 @@ int g_dense_bwd_waves = 0;   // ha_tune_set("dense_bwd_waves"): wave-count targe
 extern int g_layer_finish, g_gemm_rm, g_rollout_groups, g_gemm_ks, g_gemm_fold, g_rollout_persist, g_rollout_persist_bwd, g_rollout_persist_inject, g_rollout_pipe, g_rollout_pipe_bwd;   // rollout.hip
 extern unsigned g_cu_poison;   // debug.hip
 extern int g_loss_merge;       // fitloss.hip
+extern int g_turn_merge;       // fitpost.hip
 }
 extern "C" int ha_tune_set(const char* key, int value) {
   HA_REQUIRE(key, "ha_tune_set: null key");
@@ -65,13 +66,14 @@ extern "C" int ha_tune_set(const char* key, int value) {
   if (strcmp(key, "rollout_pipe") == 0) { ha::g_rollout_pipe = value; return HA_OK; }
   if (strcmp(key, "rollout_pipe_bwd") == 0) { ha::g_rollout_pipe_bwd = value; return HA_OK; }
   if (strcmp(key, "loss_merge") == 0) { ha::g_loss_merge = value; return HA_OK; }
+  if (strcmp(key, "turn_merge") == 0) { ha::g_turn_merge = value; return HA_OK; }
   if (strcmp(key, "rollout_persist_inject") == 0) { ha::g_rollout_persist_inject = value; return HA_OK; }
   if (strcmp(key, "cu_poison") == 0) { ha::g_cu_poison = (unsigned)value; return HA_OK; }
   ha::set_error("ha_tune_set: unknown key '%s'", key);
   return HA_ERR_INVALID_ARG;
 }
 extern "C" const char* ha_last_error(void) { return ha::g_err; }
-extern "C" int ha_abi_version(void) { return 7; }
+extern "C" int ha_abi_version(void) { return 8; }
 extern "C" int ha_device_arch(int device, char* buf, int buflen) {
   HA_REQUIRE(buf && buflen > 0, "ha_device_arch: null buffer");
   hipDeviceProp_t prop;

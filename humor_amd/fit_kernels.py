@@ -26,6 +26,7 @@ DIFF_INPUTS = [('cam_jtr', 'g_cam_jtr'), ('cam_verts', 'g_cam_verts'), ('pri_joi
                # inputs of the folded init-state prior only (spec['gmm']): their gradients come from the mixture blocks of ha_fit_loss
                ('joints_vel', None), ('trans_vel', None), ('root_orient_vel', None)]
 GMM_INPUTS = ('joints_vel', 'trans_vel', 'root_orient_vel')
+_I_PRIOR_MU = [n for n, _ in DIFF_INPUTS].index('prior_mu')      # (prior_var follows it)
 CONST_INPUTS = ['obs_j2d', 'smpl2op', 'op_mask', 'cam_f', 'cam_c', 'obs_j3d', 'obs_v3d', 'obs_floor', 'overlap']
 
 
@@ -119,6 +120,7 @@ class FusedFit(torch.autograd.Function):
             a.gmm_total = base + (ng + NT + 1) * esz
         lib.call('ha_fit_loss', C.byref(a), _lib.stream_ptr(ref))
         ctx.flat, ctx.views, ctx.ng = flat, views, ng
+        ctx.prior_key = named['prior_mu'].data_ptr() if 'prior_mu' in named and 'prior_var' in named else None
         ctx.set_materialize_grads(False)
         loss, terms, gmm_total = flat[ng + NT], flat[ng:ng + NT], flat[ng + NT + 1]
         ctx.mark_non_differentiable(terms, gmm_total)
@@ -137,6 +139,11 @@ class FusedFit(torch.autograd.Function):
         else:
             scaled = ctx.flat[:ctx.ng] * g_loss       # one launch for all inputs
         out = [None if v is None else scaled[v[0]:v[0] + v[1]].view(v[2]) for v in ctx.views]
+        if ctx.prior_key is not None:
+            # the gradients of the roll-out's prior outputs exist from here on: Stage3Body's backward, which runs before the roll-out's, lays
+            # them out for the prior's adjoint in a launch of its own (humor_amd/turn.py)
+            from . import turn as _turn
+            _turn.offer_prior_grads(g_loss.device, ctx.prior_key, out[_I_PRIOR_MU], out[_I_PRIOR_MU + 1])
         return (None, None) + tuple(out)
 
 

@@ -140,20 +140,37 @@ class _RolloutFunction(torch.autograd.Function):
     """(past_in0 [B,339], z_seq [B,S,48]) -> (world [B,S,348], prior_mu [B,S,48], prior_var [B,S,48])."""
 
     @staticmethod
-    def forward(ctx, past_in0, z_seq, handle, want_prior, z_thru=False):
+    def forward(ctx, past_in0, z_seq, handle, want_prior, z_thru=False, turn=None):
         lib = handle.lib
         z_in = z_seq
         past_in0, z_seq = past_in0.contiguous().float(), z_seq.contiguous().float()
         B, S = z_seq.shape[0], z_seq.shape[1]
         dev = past_in0.device
-        n = C.c_int64()
-        lib.call('ha_humor_rollout_workspace', handle.ptr, B, S, C.byref(n))
-        stash = torch.empty(n.value, dtype=torch.float32, device=dev)
+        # turn (humor_amd/turn.py): the box the nodes of a stage-3 evaluation share.  The head may have made the stash already and cleared the
+        # persistent kernel's exchange words in its own launch (flags: what it claims; the entry point checks the claim)
+        stash, flags = None, 0
+        if turn is not None:
+            if turn.get('handle') is not handle:
+                turn = None
+            else:
+                pre = turn.pop('fwd', None)
+                if pre is not None and pre[0] == (B, S):
+                    stash, flags = pre[1], pre[2]
+        if stash is None:
+            n = C.c_int64()
+            lib.call('ha_humor_rollout_workspace', handle.ptr, B, S, C.byref(n))
+            stash = torch.empty(n.value, dtype=torch.float32, device=dev)
         world = torch.empty(B, S, 348, dtype=torch.float32, device=dev)
         pm = torch.empty(B, S, 48, dtype=torch.float32, device=dev) if want_prior else None
         pv = torch.empty(B, S, 48, dtype=torch.float32, device=dev) if want_prior else None
-        lib.call('ha_humor_rollout_forward', handle.ptr, B, S, _lib.ptr(past_in0), _lib.ptr(z_seq), _lib.ptr(world),
-                 _lib.ptr(pm), _lib.ptr(pv), _lib.ptr(stash), _lib.stream_ptr(past_in0))
+        lib.call('ha_humor_rollout_forward_fl', handle.ptr, B, S, _lib.ptr(past_in0), _lib.ptr(z_seq), _lib.ptr(world),
+                 _lib.ptr(pm), _lib.ptr(pv), _lib.ptr(stash), flags, _lib.stream_ptr(past_in0))
+        if turn is not None:
+            turn['stash'], turn['dims'] = stash, (B, S)
+            if pm is not None:
+                from . import turn as _turn
+                _turn.expect_prior_grads(turn, pm)
+        ctx.turn = turn
         ctx.handle, ctx.stash, ctx.dims, ctx.want_prior = handle, stash, (B, S), want_prior
         ctx.save_for_backward(z_seq)
         ctx.set_materialize_grads(False)
@@ -171,9 +188,26 @@ class _RolloutFunction(torch.autograd.Function):
         g_world, g_pm, g_pv, g_z_thru = c(g_world), c(g_pm), c(g_pv), c(g_z_thru)
         g_past = torch.empty(B, 339, dtype=torch.float32, device=dev)
         g_z = torch.empty(B, S, 48, dtype=torch.float32, device=dev)
-        lib.call('ha_humor_rollout_backward_ex', handle.ptr, B, S, _lib.ptr(z_seq), _lib.ptr(g_world), _lib.ptr(g_pm), _lib.ptr(g_pv),
-                 _lib.ptr(ctx.stash), _lib.ptr(g_past), _lib.ptr(g_z), _lib.ptr(g_z_thru), _lib.stream_ptr(z_seq))
-        return g_past, g_z, None, None, None
+        flags, turn = 0, ctx.turn
+        if turn is not None and turn.get('stash') is ctx.stash:
+            # what Stage3Body's backward has done in this call's place (the layout pass only counts for the very gradients that arrive here)
+            done = turn.pop('adj', None)
+            if done is not None:
+                flags |= done[0] & _lib.ROLL_CLEARED
+                if done[0] & _lib.ROLL_LAID_OUT and done[1] == (None if g_pm is None else g_pm.data_ptr(), None if g_pv is None else g_pv.data_ptr()):
+                    flags |= _lib.ROLL_LAID_OUT
+            # the dL/dz reduction rides in Stage3Head's backward when that is certain to follow (the initial state needs its gradient) and
+            # nothing reads g_z before: z is the optimisation variable itself, whose gradient autograd only keeps
+            if turn.get('z_leaf') is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
+                from . import turn as _turn
+                t = _turn.tasks(turn, lib, B, S, ctx.stash, True)
+                if t.flags & _lib.ROLL_DEFER_DZ:
+                    flags |= _lib.ROLL_DEFER_DZ
+                    # (addresses only: a second reference to g_z would make autograd copy it into .grad before it is written)
+                    turn['dz'] = (t.dz_part, t.dz_slots, g_z.data_ptr(), g_z_thru, B, S)
+        lib.call('ha_humor_rollout_backward_fl', handle.ptr, B, S, _lib.ptr(z_seq), _lib.ptr(g_world), _lib.ptr(g_pm), _lib.ptr(g_pv),
+                 _lib.ptr(ctx.stash), _lib.ptr(g_past), _lib.ptr(g_z), _lib.ptr(g_z_thru), flags, _lib.stream_ptr(z_seq))
+        return g_past, g_z, None, None, None, None
 
 
 class _RolloutSmplJointsFunction(torch.autograd.Function):
@@ -592,7 +626,8 @@ class HumorModel(nn.Module):
         return None if cached is None else cached[1]
 
     def roll_out(self, x_past, init_input_dict, num_steps, use_mean=False, z_seq=None, return_prior=False, gender=None,
-                 betas=None, return_z=False, canonicalize_input=False, uncanonicalize_output=False, eps_seq=None, return_world=False):
+                 betas=None, return_z=False, canonicalize_input=False, uncanonicalize_output=False, eps_seq=None, return_world=False,
+                 turn=None):
         '''
         Rolls the model out from the initial state (humor_model.py:785-1017): with the given latent sequence (differentiable,
         the fitting path) or, with z_seq=None, sampling z_t = mu_t + eps_t * sigma_t from the conditional prior at every step
@@ -658,7 +693,9 @@ class HumorModel(nn.Module):
             world, pm, pv, z_out = _rollout_sample(handle, past_in.detach(), eps, num_steps)
         else:
             z_seq = z_seq[:, :num_steps]
-            world, pm, pv, z_t = _RolloutFunction.apply(past_in, z_seq, handle, bool(return_prior), bool(return_world and return_z))
+            # (turn: the box of a stage-3 evaluation, humor_amd/turn.py -- only this node takes part in its hand-overs)
+            world, pm, pv, z_t = _RolloutFunction.apply(past_in, z_seq, handle, bool(return_prior), bool(return_world and return_z),
+                                                        None if canonicalize_input else turn)
             z_out = z_seq if z_t is None else z_t
         if canonicalize_input and uncanonicalize_output:
             from .frames import uncanonicalize_world

@@ -735,17 +735,26 @@ class MotionOptimizer():
                 if r is not None:
                     place[k] = r.reshape(shapes[k]) if k in shapes else r
             cfg = dict(cfg, grad_out=place)
+        latent_motion = L(self.latent_motion)
+        if tune_phase:
+            latent_motion = latent_motion[:, :(n_init - 1)]
+        # the box the nodes share with the roll-out node for the turn-around riders (humor_amd/turn.py): a plain prior on the fused roll-out
+        turn_kw = {}
+        mp = self.motion_prior
+        if (not self._feedback_prior() and trans.is_cuda and getattr(mp, 'in_rot_rep', None) == 'mat' and getattr(mp, 'steps_in', None) == 1
+                and hasattr(mp, '_net_handle')):
+            from . import turn as _turn
+            box = _turn.new_box(mp._net_handle(trans.device), latent_motion.size(1),
+                                z_leaf=latent_motion if latent_motion is self.latent_motion and latent_motion.is_leaf else None)
+            cfg, turn_kw = dict(cfg, turn=box), dict(turn=box)
         (pose0, past_in, trans_p, root_p, joints_p, c2p_R, c2p_t, root_h, floor_t, tv_t, jv_t, rv_t, betas_t) = Stage3Head.apply(
             cfg, L(self.latent_pose).reshape(B, -1), trans.reshape(B, 3), root_orient.reshape(B, 3), betas, floor, tv.reshape(B, 3),
             jv.reshape(B, 22, 3), rv.reshape(B, 3))
         if self.shard is None:
             self.cam2prior_R, self.cam2prior_t, self.cam2prior_root_height = c2p_R, c2p_t, root_h
-        latent_motion = L(self.latent_motion)
-        if tune_phase:
-            latent_motion = latent_motion[:, :(n_init - 1)]
         # (a feedback prior reads the betas handed through the head, so that their gradients meet inside Stage3Head)
         res = self.motion_prior.roll_out(past_in.unsqueeze(1), None, latent_motion.size(1), z_seq=latent_motion, return_prior=self.cond_prior,
-                                         return_world=True, return_z=True, **self._feedback_kwargs(B, betas_t, fit_gender))
+                                         return_world=True, return_z=True, **turn_kw, **self._feedback_kwargs(B, betas_t, fit_gender))
         world, prior_out, z_t = res if self.cond_prior else (res[0], None, res[1])
         (pri_jtr, pri_verts, cam_jtr, cam_verts, r_trans, r_root, r_pose, ro_joints, conf, contacts, _cam_trans, _cam_root, betas_t) = Stage3Body.apply(
             cfg, world, trans_p, root_p, pose0, joints_p, c2p_R, c2p_t, betas_t)

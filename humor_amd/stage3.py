@@ -15,12 +15,16 @@ Inside a node the gradient that a second reader contributes is passed to the ker
 ha_fit_pre_backward, ha_rigid_image_backward, ha_humor_rollout_backward_ex: `out = adjoint + addend` in the kernel); a tensor that a later
 node also reads is handed through the earlier node as an extra output ("thru"), so its two gradients meet inside that node.  The
 arithmetic of every kernel is unchanged; only the order in which gradient contributions are summed differs (fp32 rounding).
+
+cfg['turn'] (humor_amd/turn.py): the box this evaluation's nodes share with the roll-out node.  Short launches at the ends of the persistent
+roll-out kernels that depend on nothing here ride as extra blocks of ha_fit_pre_forward / ha_rollout_post_backward / ha_fit_pre_backward.
 """
 import ctypes as C
 
 import torch
 
 from . import _lib
+from . import turn as _turn
 
 
 def _new(dev, *sh):
@@ -92,6 +96,17 @@ class Stage3Head(torch.autograd.Function):
         for k, v in dict(floor=fl, trans0=tr, root0=ro, pose0=pose0, jcam=joints, trans_vel=tv, joints_vel=jv, root_orient_vel=rv, **out).items():
             setattr(a, k, v.data_ptr())
         a.jcam_stride = jrows * 3
+        box = cfg.get('turn')
+        if box is not None:
+            # the roll-out's stash is made here, so that this launch can clear the exchange words of the persistent forward behind it
+            hnd, S = box['handle'], box['S']
+            n = C.c_int64()
+            lib.call('ha_humor_rollout_workspace', hnd.ptr, B, S, C.byref(n))
+            stash = _new(dev, n.value)
+            t = _turn.tasks(box, lib, B, S, stash, False)
+            if t.flags & _lib.ROLL_CLEARED:
+                a.clr, a.clr_words = t.clr, t.clr_words
+            box['fwd'] = ((B, S), stash, t.flags & _lib.ROLL_CLEARED)
         lib.call('ha_fit_pre_forward', C.byref(a), st)
         ctx.cfg, ctx.vws, ctx.slot, ctx.n_head, ctx.jrows = cfg, vws, slot, n_head, jrows
         ctx.save_for_backward(z, tr, ro, be, fl, tv, jv, rv, pose0, joints)
@@ -124,7 +139,19 @@ class Stage3Head(torch.autograd.Function):
             if v is not None:
                 setattr(a, k, v.data_ptr())
         a.jcam_stride = ctx.jrows * 3
+        box = cfg.get('turn')
+        dz = box.pop('dz', None) if box is not None else None
+        if dz is not None:
+            # the persistent adjoint in front left its dL/dz partials unreduced: this launch adds them up (into the roll-out node's g_z)
+            a.dz_part, a.dz_slots, a.dz_g_z, a.dz_B, a.dz_S = dz[0], dz[1], dz[2], dz[4], dz[5]
+            if dz[3] is not None:
+                a.dz_g_z_add = dz[3].data_ptr()
         lib.call('ha_fit_pre_backward', C.byref(a), st)
+        if dz is not None:
+            g = box['z_leaf'].grad
+            if g is not None and g.data_ptr() != dz[2]:
+                raise _lib.HumorAmdError('Stage3Head.backward: the roll-out node\'s g_z was copied before its reduction ran (the latent sequence\'s '
+                                         '.grad is not that tensor): ha_tune_set("turn_merge") without HA_TURN_DZ avoids the deferred reduction')
         # frame-0 SMPL adjoint: joint gradients = dL/djcam (22 rows), ha_fit_pre's direct gradients of trans / root / pose as addends
         g_root, g_body = _out(cfg, 'root_orient', dev, B, 3), _new(dev, B, 63)
         g_betas, g_transl = _out(cfg, 'betas', dev, B, be.shape[1]), _out(cfg, 'trans', dev, B, 3)
@@ -232,5 +259,25 @@ class Stage3Body(torch.autograd.Function):
             if v is not None:
                 setattr(a, k, v.data_ptr())
         a.sum_W = NB
+        box = cfg.get('turn')
+        if box is not None and box.get('dims') == (B, S) and box.get('stash') is not None:
+            # riders of the reduction launch: the layout pass of the prior's adjoint (the loss node has handed its gradients of prior_mu /
+            # prior_var over) and the clear of the persistent adjoint's exchange words; the roll-out node's backward, next, is told so
+            t = _turn.tasks(box, lib, B, S, box['stash'], True)
+            done, laid = 0, None
+            if t.flags & _lib.ROLL_CLEARED:
+                a.clr, a.clr_words = t.clr, t.clr_words
+                done |= _lib.ROLL_CLEARED
+            gp = box.pop('g_prior', None)
+            if t.flags & _lib.ROLL_LAID_OUT and gp is not None:
+                ok = lambda g: g is None or (tuple(g.shape) == (B, S, 48) and g.dtype is torch.float32 and g.is_contiguous() and g.device == dev)
+                if ok(gp[0]) and ok(gp[1]) and (gp[0] is not None or gp[1] is not None):
+                    for k, g in (('lay_g_mu', gp[0]), ('lay_g_var', gp[1])):
+                        if g is not None:
+                            setattr(a, k, g.data_ptr())
+                    a.lay_pri_out, a.lay_dst, a.lay_step_stride, a.lay_RT, a.lay_pad = t.lay_pri_out, t.lay_dst, t.lay_step_stride, t.lay_RT, t.lay_pad
+                    done |= _lib.ROLL_LAID_OUT
+                    laid = (None if gp[0] is None else gp[0].data_ptr(), None if gp[1] is None else gp[1].data_ptr())
+            box['adj'] = (done, laid)
         lib.call('ha_rollout_post_backward', C.byref(a), st)
         return None, gw, gt0, gr0, gp0, gj0, gR, gt, g_betas

@@ -30,16 +30,19 @@ extern "C" {
 #define HA_ERR_UNSUPPORTED 3   /* valid request this build cannot serve */
 
 const char* ha_last_error(void);
-/* ABI version of this header (5: + ha_humor_rollout_smpl_joints_fwd / _bwd; 6: + ha_points_fit_*; 7: ha_fit_args.gmm, the row-sum task of ha_rollout_post_args, "loss_merge"); bumped on any signature change or addition. */
+/* ABI version of this header (5: + ha_humor_rollout_smpl_joints_fwd / _bwd; 6: + ha_points_fit_*; 7: ha_fit_args.gmm, the row-sum task of ha_rollout_post_args, "loss_merge"; 8: the turn-around riders of ha_fit_pre_args / ha_rollout_post_args, ha_humor_rollout_turn_tasks, ha_humor_rollout_forward_fl / _backward_fl, "turn_merge"); bumped on any signature change or addition. */
 int ha_abi_version(void);
 /* Writes the device's gcnArchName (e.g. "gfx950:sramecc+:xnack-") into buf. */
 int ha_device_arch(int device, char* buf, int buflen);
-/* Development knobs for kernel launch variants (A/B measurements), process-wide: "skin_variant" (-1 = auto), "layer_finish" (0 never / 1 auto / 2 always use the GroupNorm finishing pass), "gemm_rm" (row tiles per wave of the batched prior GEMM: 0 by size / 1 / 2), "gemm_ks" (short-chain forms of the small batched GEMMs: 0 = plain form everywhere, 2 = by the launch policy, 3 = force the deepest K split), "gemm_fold" (1 = the layout-only passes around the batched GEMMs -- prior_mu / prior_var of a roll-out, y / g_x / a narrow x of ha_mlp_* -- are done by the GEMM itself, 0 = separate launches), "rollout_persist" / "rollout_persist_bwd" (0 = launch chain; 1 = persistent kernels, 3 = with write-through publishes), "rollout_pipe" / "rollout_pipe_bwd" (batches of more than 32 sequences: 1 = the layer-parallel pipelined persistent kernels, 0 = launch chain; set the adjoint knobs before the forward call), "loss_merge" (1 = ha_fit_loss runs the folded init-state prior inside its own two launches, its reduction reads the per-frame partial sums through the LDS, and ha_rollout_post_backward's reduction launch also does its row-sum task; 0 = one launch per kernel, as up to ABI 6), "rollout_persist_inject" (test hook: 1 = the next persistent forwards drop one CU of team 0, so that the failure path -- NaN results, error word -- can be exercised), "cu_poison" (test hook: != 0 = every kernel launch of this library is preceded by a kernel that fills the LDS and the vector registers of every CU with a bit pattern -- 1 = a quiet NaN, else the value itself -- so that a read of state the kernel did not write shows on every box). */
+/* Development knobs for kernel launch variants (A/B measurements), process-wide: "skin_variant" (-1 = auto), "layer_finish" (0 never / 1 auto / 2 always use the GroupNorm finishing pass), "gemm_rm" (row tiles per wave of the batched prior GEMM: 0 by size / 1 / 2), "gemm_ks" (short-chain forms of the small batched GEMMs: 0 = plain form everywhere, 2 = by the launch policy, 3 = force the deepest K split), "gemm_fold" (1 = the layout-only passes around the batched GEMMs -- prior_mu / prior_var of a roll-out, y / g_x / a narrow x of ha_mlp_* -- are done by the GEMM itself, 0 = separate launches), "rollout_persist" / "rollout_persist_bwd" (0 = launch chain; 1 = persistent kernels, 3 = with write-through publishes), "rollout_pipe" / "rollout_pipe_bwd" (batches of more than 32 sequences: 1 = the layer-parallel pipelined persistent kernels, 0 = launch chain; set the adjoint knobs before the forward call), "loss_merge" (1 = ha_fit_loss runs the folded init-state prior inside its own two launches, its reduction reads the per-frame partial sums through the LDS, and ha_rollout_post_backward's reduction launch also does its row-sum task; 0 = one launch per kernel, as up to ABI 6), "turn_merge" (bits HA_TURN_DZ | HA_TURN_POST | HA_TURN_FWD_CLEAR, default all: the short launches at the ends of the B <= 32 persistent roll-out kernels ride as block roles in ha_fit_pre_backward / ha_rollout_post_backward / ha_fit_pre_forward -- see ha_humor_rollout_turn_tasks; 0 = each keeps its own launch, as up to ABI 7), "rollout_persist_inject" (test hook: 1 = the next persistent forwards drop one CU of team 0, so that the failure path -- NaN results, error word -- can be exercised), "cu_poison" (test hook: != 0 = every kernel launch of this library is preceded by a kernel that fills the LDS and the vector registers of every CU with a bit pattern -- 1 = a quiet NaN, else the value itself -- so that a read of state the kernel did not write shows on every box). */
 int ha_tune_set(const char* key, int value);
 /* Test support: fills the LDS and every VGPR / AGPR of all CUs with `pattern` (0 = quiet NaN) on `stream`; with `surviving_words` non-null it then
  * synchronises the stream and counts the LDS words (of 256 x 40960) a following kernel still finds holding the pattern -- 0 means this box clears
  * LDS between kernels and the hook cannot show anything. */
 int ha_debug_cu_poison(unsigned int pattern, unsigned int* surviving_words, void* stream);
+/* Test support (ABI 8): the number of kernels this library has launched in this process so far (the poison kernels of "cu_poison" not counted);
+ * the difference across a piece of host code is its launch count, whether the launches ran eagerly or were captured into a hipGraph. */
+int ha_debug_launch_count(unsigned long long* launches);
 
 /* ------------------------------------------------------------------------------------------------
  * SMPL / SMPL+H body model  (replaces smplx==0.1.28 `lbs`, `SMPLH.forward`, `VertexJointSelector` as
@@ -262,6 +265,43 @@ int ha_humor_rollout_backward_ex(const ha_humor_net* net, int B, int S, const fl
                                  const float* g_world, const float* g_prior_mu, const float* g_prior_var,
                                  float* stash, float* g_past_in0, float* g_z_seq, const float* g_z_add, void* stream);
 
+/* Turn-around riders (ABI 8).  Around the one-launch roll-out of B <= 32 sequences three short launches depend on nothing their
+ * neighbours write: the clear of the persistent kernels' exchange words (forward and adjoint), the layout pass that turns g_prior_mu /
+ * g_prior_var into the slab the prior's adjoint reads, and the reduction of the adjoint's dL/dz partials.  Another entry point of this
+ * library can run them as extra blocks of a launch it makes anyway (ha_fit_pre_forward: the forward's clear; ha_rollout_post_backward:
+ * the layout pass and the adjoint's clear; ha_fit_pre_backward: the dL/dz reduction); the roll-out entry point is then told so with
+ * flag bits and skips them.
+ *   ha_humor_rollout_turn_tasks(net, B, S, stash, adjoint, out): what may ride for the call ha_humor_rollout_forward (adjoint = 0, asked
+ *     before it) or ha_humor_rollout_backward (adjoint = 1, asked after the forward over `stash`) is about to make -- regions inside
+ *     `stash`, and out->flags = the HA_ROLL_* bits the roll-out entry point accepts.  All zero when the call does not run the B <= 32
+ *     persistent kernels (launch chain, pipelined kernels, several row groups) or "turn_merge" has the part's bit off.
+ *   ha_humor_rollout_forward_fl / _backward_fl: ha_humor_rollout_forward / _backward_ex with `flags`.
+ *     HA_ROLL_CLEARED: the exchange words are zero -- a launch given the `clr` task has been issued on this stream, behind every earlier
+ *       reader of them.  HA_ROLL_LAID_OUT (adjoint): a launch given the layout task for these g_prior_mu / g_prior_var has been issued.
+ *       Each is checked on the host against a record the riding launch leaves for the region: a call flagged for a region no launch has
+ *       treated since its last use returns HA_ERR_INVALID_ARG before anything is launched; so does a flag the call's path cannot honour.
+ *     HA_ROLL_DEFER_DZ (adjoint): g_z_seq is NOT written; the partials stay in the stash until ha_fit_pre_backward is given the dz task
+ *       (dz_part of the query, this call's g_z_seq and g_z_add) on the same stream.  Until that has happened every roll-out entry point
+ *       on this network returns HA_ERR_INVALID_ARG: partials that nobody picked up are never silently a zero gradient. */
+#define HA_TURN_DZ 1
+#define HA_TURN_POST 2
+#define HA_TURN_FWD_CLEAR 4
+#define HA_ROLL_CLEARED 1u
+#define HA_ROLL_LAID_OUT 2u
+#define HA_ROLL_DEFER_DZ 4u
+typedef struct ha_turn_tasks {
+  unsigned int flags;                      /* HA_ROLL_* bits the roll-out call accepts */
+  void* clr; int64_t clr_words;            /* exchange words of the persistent kernels (4-byte words) */
+  const float* lay_pri_out; float* lay_dst; int64_t lay_step_stride; int lay_RT; int lay_pad;   /* adjoint: the layout pass */
+  const float* dz_part; int dz_slots;      /* adjoint: the dL/dz partials [S][dz_slots][32][48] */
+} ha_turn_tasks;
+int ha_humor_rollout_turn_tasks(const ha_humor_net* net, int B, int S, float* stash, int adjoint, ha_turn_tasks* out);
+int ha_humor_rollout_forward_fl(const ha_humor_net* net, int B, int S, const float* past_in0, const float* z_seq,
+                                float* world, float* prior_mu, float* prior_var, float* stash, unsigned int flags, void* stream);
+int ha_humor_rollout_backward_fl(const ha_humor_net* net, int B, int S, const float* z_seq,
+                                 const float* g_world, const float* g_prior_mu, const float* g_prior_var,
+                                 float* stash, float* g_past_in0, float* g_z_seq, const float* g_z_add, unsigned int flags, void* stream);
+
 /* Per-network options.  "output_delta" (default 1): the decoder emits residuals that are composed with the input state
  * (HumorModel(output_delta=True), humor/models/humor_model.py:460-494); 0: it emits the next state itself and only its rotations are
  * converted (humor_model.py:331-347).  Networks with output_delta = 0 run the launch chain. */
@@ -401,6 +441,12 @@ typedef struct ha_fit_pre_args {
    * added to the corresponding output in the kernel instead of by an accumulation launch behind it. */
   int jcam_stride;
   const float* add_floor; const float* add_pose0; const float* add_trans_vel; const float* add_joints_vel; const float* add_root_orient_vel;
+  /* optional (ABI 8): turn-around riders (ha_humor_rollout_turn_tasks), extra blocks of the launch.  Forward: clr / clr_words, the exchange
+   * words to zero (clr NULL = none).  Backward: the dL/dz reduction of the persistent adjoint -- dz_g_z [dz_B,dz_S,48] = sum of the
+   * dz_slots partials dz_part [dz_S][dz_slots][32][48] + dz_g_z_add (may be NULL); dz_part NULL = none.  With the part's "turn_merge" bit
+   * off the same work runs as a launch of its own in front. */
+  void* clr; int64_t clr_words;
+  const float* dz_part; float* dz_g_z; const float* dz_g_z_add; int dz_B, dz_S, dz_slots;
 } ha_fit_pre_args;
 int ha_fit_pre_forward(const ha_fit_pre_args* args, void* stream);
 int ha_fit_pre_backward(const ha_fit_pre_args* args, void* stream);
@@ -431,6 +477,13 @@ typedef struct ha_rollout_post_args {
   /* optional (ABI 7), backward only: a row-sum task that rides in the reduction launch -- sum_out [B,sum_W] = sum_t sum_src [B,T,sum_W] +
    * sum_add1 [B,sum_W] + sum_add2 [B,sum_W], exactly ha_seq_sum_add(B, T, sum_W, ...) (addends may be NULL; sum_src NULL = no task) */
   const float* sum_src; const float* sum_add1; const float* sum_add2; float* sum_out; int sum_W;
+  /* optional (ABI 8), backward only: turn-around riders of the reduction launch (ha_humor_rollout_turn_tasks).  The layout pass of the
+   * prior's adjoint: lay_dst [S][lay_RT][lay_pad][32] = g_mu | g_var * exp(log-variance) | zeros, quad-interleaved, from lay_g_mu /
+   * lay_g_var [B,S,48] (either may be NULL = zero) and the forward's output slabs lay_pri_out (step t at + t * lay_step_stride);
+   * lay_dst NULL = none.  clr / clr_words: exchange words to zero (clr NULL = none).  With "turn_merge" bit HA_TURN_POST off (or
+   * "loss_merge" 0) the same work runs as launches of its own behind the reduction. */
+  const float* lay_g_mu; const float* lay_g_var; const float* lay_pri_out; float* lay_dst; int64_t lay_step_stride; int lay_RT; int lay_pad;
+  void* clr; int64_t clr_words;
 } ha_rollout_post_args;
 int ha_rollout_post_forward(const ha_rollout_post_args* args, void* stream);
 int ha_rollout_post_backward(const ha_rollout_post_args* args, void* stream);
