@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, 'csrc', 'libhumor_amd.so')
 
 HA_OK = 0
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int32)
@@ -155,6 +155,9 @@ _SIGS = {
     'ha_rollout_post_forward': (C.c_int, [C.POINTER(RolloutPostArgs), C.c_void_p]),
     'ha_rollout_post_backward': (C.c_int, [C.POINTER(RolloutPostArgs), C.c_void_p]),
     'ha_gmm_nll': (C.c_int, [C.POINTER(GmmArgs), C.c_void_p]),
+    'ha_gmm_fit_workspace': (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int64)] * 2),
+    'ha_gmm_fit_estep': (C.c_int, [C.c_int] * 3 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_void_p]),
+    'ha_gmm_fit_mstep': (C.c_int, [C.c_int] * 3 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_void_p]),
     'ha_rigid_image_forward': (C.c_int, [C.POINTER(RigidImageArgs), C.c_void_p]),
     'ha_rigid_image_backward': (C.c_int, [C.POINTER(RigidImageArgs), C.c_void_p]),
     'ha_lbfgs_coeffs': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),

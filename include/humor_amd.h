@@ -30,7 +30,7 @@ extern "C" {
 #define HA_ERR_UNSUPPORTED 3   /* valid request this build cannot serve */
 
 const char* ha_last_error(void);
-/* ABI version of this header (5: + ha_humor_rollout_smpl_joints_fwd / _bwd; 6: + ha_points_fit_*; 7: ha_fit_args.gmm, the row-sum task of ha_rollout_post_args, "loss_merge"; 8: the turn-around riders of ha_fit_pre_args / ha_rollout_post_args, ha_humor_rollout_turn_tasks, ha_humor_rollout_forward_fl / _backward_fl, "turn_merge"); bumped on any signature change or addition. */
+/* ABI version of this header (5: + ha_humor_rollout_smpl_joints_fwd / _bwd; 6: + ha_points_fit_*; 7: ha_fit_args.gmm, the row-sum task of ha_rollout_post_args, "loss_merge"; 8: the turn-around riders of ha_fit_pre_args / ha_rollout_post_args, ha_humor_rollout_turn_tasks, ha_humor_rollout_forward_fl / _backward_fl, "turn_merge"; 9: + ha_gmm_fit_*); bumped on any signature change or addition. */
 int ha_abi_version(void);
 /* Writes the device's gcnArchName (e.g. "gfx950:sramecc+:xnack-") into buf. */
 int ha_device_arch(int device, char* buf, int buflen);
@@ -527,6 +527,26 @@ typedef struct ha_gmm_args {
   float* lp; float* gpart; float* nll; float* g_x;
 } ha_gmm_args;
 int ha_gmm_nll(const ha_gmm_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fitting that mixture (ABI 9; replaces the two data passes of scikit-learn's GaussianMixture.fit as humor/train/train_state_prior.py
+ * :97-123 drives it: full covariances): one EM iteration = ha_gmm_fit_estep, ha_gmm_fit_mstep and a small fp64 finish by the caller.
+ *   x [N, D] with a row stride of x_stride floats (>= D);  1 <= D <= 256, 1 <= K <= 64, N >= 1.
+ * E step: y = (x_n - means_k) P_k (the mean is subtracted before the product),  lp[n][k] = cst_k - |y|^2 / 2,
+ *   loglik [N] = logsumexp_k lp[n][k];  resp [N, K] = exp(lp - loglik) (NULL: not written);  ll_part [estep_blocks] = sums of loglik
+ *   over blocks of 64 rows in a fixed order.  P [K, D, D] row-major is the Cholesky factor of the precision in scikit-learn's
+ *   orientation (precisions_cholesky_);  upper = 1: it is upper triangular with its zeros stored, and rows of it that can only hold
+ *   zeros are skipped;  upper = 0: any factor.  cst [K] = log w_k + log det P_k - D/2 log 2 pi.
+ * M step, about the shift m_k = shift [K, D] (the means the E step used):  nk [K] = sum_n r[n][k],  sx [K, D] = sum r (x - m_k),
+ *   sxx [K, D, D] = sum r (x - m_k)(x - m_k)^T, exactly symmetric.  Rows are split over blocks, the per-block partials live in
+ *   ws (mstep_floats floats) and are added in a fixed order: no floating-point atomics, the same bits on every call.
+ * No host reads, no hidden synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+int ha_gmm_fit_workspace(int N, int D, int K, int64_t* estep_blocks, int64_t* mstep_floats);
+int ha_gmm_fit_estep(int N, int D, int K, const float* x, int64_t x_stride, const float* means, const float* P, int upper,
+                     const float* cst, float* resp, float* loglik, float* ll_part, void* stream);
+int ha_gmm_fit_mstep(int N, int D, int K, const float* x, int64_t x_stride, const float* resp, const float* shift, float* nk,
+                     float* sx, float* sxx, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Chamfer distance (replaces humor/utils/chamfer_distance/chamfer_distance.cu: ChamferDistanceKernelLauncher :140-157 and
